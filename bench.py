@@ -8,15 +8,24 @@ h = 0.625 (d = 0.625 N, SURVEY.md section 7 hard part 2), k = 0.2, r = 0.01, g =
 U0 = default_rng(2020).standard_normal(N^2), scipy-default tolerances, FD (scipy-faithful) JVP.
 
     python bench.py [--gpus N --steps K --warmup W]       (N > 1: starts N rank processes itself)
+    python bench.py --full [...]                          (the headline and every other leg)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does what the headline needs and no more: set up, W warmup steps, K timed steps, one
+JSON line (steps/s, ms_per_step, and the kernel figures its in-region HIP events give for free).
+--dump-outputs DIR also writes the last timed step's result to DIR/U.npy.  --full adds the legs
+that take runs of their own: the final step's oracle residual on the host (a wrong answer then
+fails the run), the live rocprofv3 passes, the isolated-JVP and copy-bandwidth probes, the CPU
+baseline and the other configs; --extra / --pmc / --probes / --cpu-baseline select among them.
 
 N > 1: the same 4096^2 grid is cut into N row slabs (strong scaling); halo exchange and
 all-reduce through the peer-memory communicator over xGMI (default) or RCCL (--comm rccl).
 value = time steps per second of the whole job (max over ranks of the timed region).
 Rank 0 prints ONE JSON line.  The kernel roofline comes from HIP events recorded around every
 kernel on the solver's stream inside the timed region (nk_sh_kernel_profile); roofline.traffic
-from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over a short child run of this bench on
-the same box after the timed region (N=1; --pmc off: the last committed profile's ratios).
+from the last committed profile's ratios, or with --full from two rocprofv3 --pmc passes
+(FETCH_SIZE, WRITE_SIZE) over a short child run of this bench on the same box after the timed
+region (N=1; --pmc off: the committed ratios again).
 """
 from __future__ import annotations
 
@@ -40,6 +49,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=4096, help="grid points per side")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the final step's oracle check, "
+                         "the rocprofv3 passes, the probes, the CPU baseline and the other "
+                         "configs (--extra / --pmc / --probes / --cpu-baseline choose among them; "
+                         "without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's result (the array "
+                         "step() returned) to DIR/U.npy as float64: the whole grid up to "
+                         "DUMP_MAX_BYTES, else its values at a fixed seeded sample of points")
     ap.add_argument("--jvp", choices=["fd", "analytic"], default="fd")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--comm", choices=["peer", "rccl"], default="peer",
@@ -59,7 +77,29 @@ def parse():
     ap.add_argument("--slab-ab", type=int, default=2,
                     help="N > 1: time steps of each slab-exchange variant after the warmup; the "
                          "fastest is the one the timed region runs (slab_exchange_ab; 0: off)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.extra = args.pmc = args.probes = args.cpu_baseline = "off"
+    return args
+
+
+DUMP_MAX_BYTES = 32 << 20  # per dumped array
+DUMP_SEED = 4096
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: ``arrays`` ({name: host array}) as path/<name>.npy in float64.  An array
+    above DUMP_MAX_BYTES is written as its values at DUMP_MAX_BYTES / 8 flat indices drawn (with
+    replacement) by default_rng(DUMP_SEED) from its size: the same points for the same shape, so
+    two builds' dumps compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.nbytes > DUMP_MAX_BYTES:
+            idx = np.random.default_rng(DUMP_SEED).integers(0, x.size, DUMP_MAX_BYTES // 8)
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def pmc_traffic(args):
@@ -77,8 +117,7 @@ def pmc_traffic(args):
         return None
     d = tempfile.mkdtemp(prefix="nkhip_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
     child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1",
-             "--n", str(args.n), "--jvp", args.jvp, "--extra", "off", "--cpu-baseline", "off",
-             "--pmc", "off", "--probes", "off"]
+             "--n", str(args.n), "--jvp", args.jvp]  # a plain run: the headline's steps alone
     t0 = time.perf_counter()
     try:
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
@@ -124,8 +163,7 @@ def trace_durations(args):
         return None
     d = tempfile.mkdtemp(prefix="nkhip_kt_", dir=os.environ.get("TMPDIR", "/tmp"))
     child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1",
-             "--n", str(args.n), "--jvp", args.jvp, "--extra", "off", "--cpu-baseline", "off",
-             "--pmc", "off", "--probes", "off"]
+             "--n", str(args.n), "--jvp", args.jvp]  # a plain run: the headline's steps alone
     try:
         r = subprocess.run([prof, "--kernel-trace", "--stats", "-d", d, "-o", "kt",
                             "--output-format", "csv", "--"] + child,
@@ -1008,26 +1046,26 @@ def main():
         elapsed = float(t.item())
     prof = model.kernel_profile()
     final_max = float(a.abs().max())
-    # check the final step on the host (outside the timed region): a = U[s+1], b = U[s]; with
-    # N > 1 the slabs are gathered to every rank and rank 0 evaluates the oracle residual
+    # --full: check the final step on the host (outside the timed region): a = U[s+1], b = U[s];
+    # with N > 1 the slabs are gathered to every rank and rank 0 evaluates the oracle residual
     # (sh_scipy_nk.py:47-49) of the whole grid.  Slabs differ in rows by at most one: gathered
-    # padded to the largest slab, then trimmed.
-    if world > 1:
+    # padded to the largest slab, then trimmed.  --dump-outputs writes the same U[s+1].
+    def gather(x):
+        if world == 1:
+            return x.cpu().numpy()
         nys = [nkhip.slab_rows(n, q, world)[1] for q in range(world)]
-        nymax = max(nys)
+        xp = torch.zeros((max(nys), n), dtype=x.dtype, device=coll_dev)
+        xp[:ny] = x.to(coll_dev)
+        parts = [torch.empty_like(xp) for _ in range(world)]
+        dist.all_gather(parts, xp)
+        if rank != 0:
+            return None
+        return torch.cat([p_[:nq] for p_, nq in zip(parts, nys)]).cpu().numpy()
 
-        def gather(x):
-            xp = torch.zeros((nymax, n), dtype=x.dtype, device=coll_dev)
-            xp[:ny] = x.to(coll_dev)
-            parts = [torch.empty_like(xp) for _ in range(world)]
-            dist.all_gather(parts, xp)
-            if rank != 0:
-                return None
-            return torch.cat([p_[:nq] for p_, nq in zip(parts, nys)]).cpu().numpy()
-
-        full_a, full_b = gather(a), gather(b)
-    else:
-        full_a, full_b = a.cpu().numpy(), b.cpu().numpy()
+    full_a = gather(a) if (args.full or args.dump_outputs) else None
+    full_b = gather(b) if args.full else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"U": full_a})
     # config 5 on this job's ranks (N > 1): the point of the 16384^2 curve; at N = 1 it runs
     # below, in other_configs.config5_1gpu
     c5 = None
@@ -1080,14 +1118,16 @@ def main():
                                        f"{traffic_db.get('source')}); not measured in this run")
                     if traffic else None}
 
-        from oracle import sh_oracle
-        F_last = sh_oracle.residual(full_a.reshape(-1), full_b.reshape(-1), n, n, h, r, k, g)
-        final_check = {"max_abs_residual": float(np.abs(F_last).max()),
-                       "f_tol": float(np.finfo(float).eps ** (1 / 3)),
-                       "what": "oracle residual (sh_scipy_nk.py:47-49) of the last timed step, "
-                               "evaluated on the host over the whole grid; above f_tol the "
-                               "bench exits non-zero after printing its line"}
-        del F_last
+        final_check = None
+        if args.full:
+            from oracle import sh_oracle
+            F_last = sh_oracle.residual(full_a.reshape(-1), full_b.reshape(-1), n, n, h, r, k, g)
+            final_check = {"max_abs_residual": float(np.abs(F_last).max()),
+                           "f_tol": float(np.finfo(float).eps ** (1 / 3)),
+                           "what": "oracle residual (sh_scipy_nk.py:47-49) of the last timed "
+                                   "step, evaluated on the host over the whole grid; above f_tol "
+                                   "the bench exits non-zero after printing its line"}
+            del F_last
         jvp_name = "sh_fdjvp" if args.jvp == "fd" else "sh_ajvp"
         kernel_ms = sum(v["ms_est"] for v in ker.values())
         out = {
@@ -1097,6 +1137,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True,
             "scaling": "strong",
@@ -1189,11 +1230,10 @@ def main():
         # a wrong answer fails the run (sh_scipy_nk.py:47-49: the step is a root to f_tol in the
         # max norm; the slack covers the oracle's own rounding, ~1e-14 at these magnitudes)
         c4 = out.get("other_configs", {}).get("config4_100") or {}
-        for what, v, tol in (("headline", final_check["max_abs_residual"], final_check["f_tol"]),
-                             ("config5", (c5 or {}).get("final_step_residual", 0.0),
-                              final_check["f_tol"]),
-                             ("config4_100", c4.get("final_step_residual", 0.0),
-                              final_check["f_tol"])):
+        f_tol = float(np.finfo(float).eps ** (1 / 3))
+        for what, v, tol in (("headline", (final_check or {}).get("max_abs_residual", 0.0), f_tol),
+                             ("config5", (c5 or {}).get("final_step_residual", 0.0), f_tol),
+                             ("config4_100", c4.get("final_step_residual", 0.0), f_tol)):
             if not v <= tol + 1e-12:
                 print(f"bench: {what} final-step residual {v:.3e} exceeds f_tol {tol:.3e}",
                       file=sys.stderr)

@@ -7,8 +7,9 @@ does (``sh_scipy_nk.py:53-61``):
 ``nk_n4096_h0625_sampled.npz``  (config 4: 4096^2, d = 0.625 N = 2560, SURVEY 7 hard part 2)
     ONE implicit step from ``U0 = default_rng(2020).standard_normal(4096^2)`` at SciPy's default
     tolerances.  A 4096^2 state is 134 MB, so only a sample is stored: 64 strided rows of U1
-    (rows 0, 64, 128, ...; 2 MB), the sum of every row of U1 (4096 values), max|U1| and the
-    reference's Newton-iteration and F-eval counts.  The GPU test regenerates U0 from the seed.
+    (rows 0, 64, 128, ...; 2 MB, written as three blocks ``..._sampled_rows{0,1,2}.npz``), the
+    sum of every row of U1 (4096 values), max|U1| and the reference's Newton-iteration and
+    F-eval counts.  The GPU test regenerates U0 from the seed.
 
 ``nk_n64_traj100.npz``  (the reference defaults: N = 64, d = 40, sh_scipy_nk.py:15-16)
     100 consecutive steps of the loop from ``U0 = default_rng(2020).standard_normal(64^2)``
@@ -73,6 +74,12 @@ def main():
     cases = {"nk_n64_traj100": traj_case()}
     if "--traj-only" not in sys.argv:
         cases["nk_n4096_h0625_sampled"] = config4_case()
+    if "nk_n4096_h0625_sampled" in cases:
+        # the sampled rows go into three files of their own, so that none exceeds 1 MiB
+        c4 = cases["nk_n4096_h0625_sampled"]
+        rows, U1_rows = c4["rows"], c4.pop("U1_rows")
+        for i, sel in enumerate(np.array_split(np.arange(len(rows)), 3)):
+            cases[f"nk_n4096_h0625_sampled_rows{i}"] = dict(rows=rows[sel], U1_rows=U1_rows[sel])
     for name, arrs in cases.items():
         np.savez_compressed(os.path.join(OUT, name + ".npz"),
                             **{k: np.asarray(v) for k, v in arrs.items()})

@@ -5,7 +5,9 @@
 * the slab path the timed region runs is the slab A/B's fastest variant (bench.select_slab_path),
   excluding a variant that failed, with its switches left in the environment, and the path named
   from the effective switches (bench.effective_slab_path) -- over a gloo world of one, as on the
-  ranks (the choice is broadcast from rank 0).
+  ranks (the choice is broadcast from rank 0);
+* a plain run switches every leg beside the headline off (--full turns them on), and
+  --dump-outputs writes an array whole or at a fixed seeded sample of its points.
 """
 import os
 import socket
@@ -91,3 +93,33 @@ def test_select_slab_path(clean_switches, gloo_world_of_one):
                steps={"pushed": 0, "edge_halo": 5, "in_kernel": 5})
     assert bench.select_slab_path(rec, True, dist, torch) == "in_kernel"
     assert os.environ["NKHIP_SLAB_XK"] == "1"
+
+
+def test_plain_run_switches_every_extra_leg_off(monkeypatch):
+    """Without --full none of the legs beside the headline runs, whatever their own switches say;
+    with it they keep their defaults and can be chosen one by one."""
+    legs = ("extra", "pmc", "probes", "cpu_baseline")
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                                     "--extra", "on", "--pmc", "auto"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+    assert all(getattr(a, k) == "off" for k in legs), a
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--probes", "off"])
+    a = bench.parse()
+    assert a.full and (a.extra, a.pmc, a.probes, a.cpu_baseline) == ("on", "auto", "off", "auto")
+
+
+def test_dump_outputs_whole_or_seeded_sample(tmp_path):
+    """--dump-outputs: a small array is written whole, a large one as its values at the seeded
+    sample of flat indices -- the same points on every call -- in float64, within the size cap."""
+    small = np.arange(12, dtype=np.float32).reshape(3, 4)
+    big = np.random.default_rng(5).standard_normal(bench.DUMP_MAX_BYTES // 8 + 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    x, y = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert x.dtype == np.float64 and x.nbytes == bench.DUMP_MAX_BYTES <= 64 << 20
+    assert np.array_equal(x, y)
+    idx = np.random.default_rng(bench.DUMP_SEED).integers(0, big.size, x.size)
+    assert np.array_equal(x, big[idx])

@@ -21,8 +21,9 @@ def test_bench_self_launch_four_ranks_one_gpu():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["NKHIP_BENCH_ONE_DEVICE"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--n",
-                        "1024", "--steps", "2", "--warmup", "1", "--extra", "off", "--pmc", "off"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4",
+                        "--n", "1024", "--steps", "2", "--warmup", "1", "--extra", "off",
+                        "--pmc", "off"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=540)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -65,9 +66,9 @@ def test_bench_push_selftest_fault_falls_back_and_config5_leg():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(NKHIP_BENCH_ONE_DEVICE="1", NKHIP_PEER_SELFTEST_BREAK_PUSH="1",
                NKHIP_BENCH_CONFIG5_N="2048")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n",
-                        "1024", "--steps", "1", "--warmup", "1", "--extra", "on", "--pmc", "off",
-                        "--probes", "off", "--slab-ab", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2",
+                        "--n", "1024", "--steps", "1", "--warmup", "1", "--extra", "on",
+                        "--pmc", "off", "--probes", "off", "--slab-ab", "1"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=540)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -266,6 +266,11 @@ def test_config4_matches_reference_step():
     every row sum to the same bound times nx, and the Newton count to +-1."""
     import nkhip
     z = load_golden("nk_n4096_h0625_sampled")
+    # the 64 sampled rows are stored in three blocks (files of under 1 MiB each)
+    blocks = [load_golden(f"nk_n4096_h0625_sampled_rows{i}") for i in range(3)]
+    z["U1_rows"] = np.concatenate([b["U1_rows"] for b in blocks])
+    assert np.array_equal(z["rows"], np.concatenate([b["rows"] for b in blocks]))
+    assert z["U1_rows"].shape == (64, 4096)
     N = int(z["N"])
     U0 = np.random.default_rng(int(z["seed"])).standard_normal((N, N))
     m = nkhip.SwiftHohenberg(N=N, d=float(z["d"]), k=float(z["k"]), r=float(z["r"]),
