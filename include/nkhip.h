@@ -189,6 +189,23 @@ int nk_debug_bounds(int64_t* violations, int32_t* first_line, int32_t reset);
  * recomputed after kMBSpin polls.  NK_EINVAL from the other builds.  Diagnostic only: no
  * reference interface. */
 int nk_debug_mailbox(int64_t* counts, int32_t reset);
+/* One step t (1 <= t <= 34) of the device-side Arnoldi control on a
+ * synthetic loop state, through the solver's own launch of either form of the control -- form 0:
+ * the control launch that stages the Gram rows through LDS (the code the fused launches' tail
+ * also runs), form 1: the reduce + control launch that holds them in registers, on one partial
+ * per value -- so that a test can hold the two to the same bits.  The state is zero except for
+ * ints[6] = j, hn_pending, m, nv_max, halt, steps; scal[6] = wnorm[t-1], gv[t-1], sig_est[t],
+ * ptol, omega, lag_ratio2; sig[t+1]; h[t], cs[t], sn[t]; gram[t*t], row-major, of which the
+ * entries [r][k], k < r, are used; red[2(t+1)+1], the multi-dot results of step t.  Out: the
+ * byte images of the device state and of its pinned host mirror after the step (state_out ==
+ * NULL: returns their size in bytes and does nothing else), prm_out[39] the fused step's
+ * parameter block, *status_out the step's status word (0 untouched, 1 continued, 2 handed
+ * back).  Allocates, runs one launch, synchronises the device.  Diagnostic only: no reference
+ * interface. */
+int nk_debug_ctl_step(int32_t form, int32_t t, const int32_t* ints, const double* scal,
+                      const double* sig, const double* h, const double* cs, const double* sn,
+                      const double* gram, const double* red, void* state_out, void* mirror_out,
+                      double* prm_out, uint32_t* status_out);
 
 /* ---------------- communicators (row-slab decomposition over RCCL / xGMI) ---------------- */
 int nk_comm_unique_id_bytes(void);

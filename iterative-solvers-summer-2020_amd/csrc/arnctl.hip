@@ -28,6 +28,7 @@ constexpr int RB = 1024;  // reduction block (as reduce_final_kernel)
 __device__ unsigned long long g_ctl_probe[8];
 __device__ unsigned long long g_ctl_t0 = ~0ull;   // this launch's first entry (reset by the last)
 __device__ unsigned long long g_ctl_tl = 0;       // this launch's last entry
+__device__ unsigned long long g_ctl_last;         // the last block's wave past its early return
 #define CTL_STAMP(v) const unsigned long long v = wall_clock64()
 #else
 #define CTL_STAMP(v)
@@ -85,28 +86,44 @@ __global__ void __launch_bounds__(64) arn_ctl_kernel(ArnCtlState* S, ArnCtlState
   ctl_body(S, H, red, red_host, prm, status, t, G);
 }
 
+// The reducing control kernels' common part: block k sums column k of the partials, the last
+// block to finish collects every block's sum.  true: this is the last block's first wave and the
+// gridDim.x sums are in vals (LDS); everybody else is done.  The control's loads (ctl_load, first
+// wave of every block) are in flight during the reduction (they lengthen it by ~1 us, but issued
+// after it they cost more: profiles/r06_short_slab.md 9).  result_host (optional, pinned host
+// memory: not cached) receives this block's sum.
+__device__ __forceinline__ bool reduce_to_last_wave(const double* partial, int64_t nblk,
+                                                    double* result, double* result_host,
+                                                    ArnCtlState* S, int t, CtlPre& P, GramRegs& R,
+                                                    double* vals) {
+  if (threadIdx.x < 64) ctl_load(S, t, P, R);
+  const int k = blockIdx.x;
+  const double s = reduce_column<RB>(partial + int64_t(k) * nblk, nblk, true);
+  __shared__ bool last;
+  if (threadIdx.x == 0) {
+    // written through and drained before counting in (reduced_arrive)
+    st_sc1(result + k, s);
+    if (result_host) result_host[k] = s;
+    last = reduced_arrive(S);
+  }
+  __syncthreads();
+  if (!last || threadIdx.x >= 64) return false;
+#ifdef ARN_CTL_PROBE
+  if (threadIdx.x == 0) g_ctl_last = wall_clock64();  // read back by the same thread
+#endif
+  reduced_collect(S, result, vals, int(gridDim.x));
+  return true;
+}
+
 __global__ void __launch_bounds__(RB) arn_reduce_ctl_kernel(const double* partial, int64_t nblk,
                                                             double* result, double* result_host,
                                                             ArnCtlState* S, ArnCtlState* H,
                                                             double* prm, uint32_t* status, int t) {
-  // the control's loads (first wave of every block), in flight during the reduction (they
-  // lengthen it by ~1 us, but issued after it they cost more: profiles/r06_short_slab.md 9)
   CtlPre P;
-  if (threadIdx.x < 64) ctl_load(S, t, P);
-  const int k = blockIdx.x;
-  const double s = reduce_column<RB>(partial + int64_t(k) * nblk, nblk, true);
-  __shared__ bool last;
+  GramRegs R;
   __shared__ double vals[kRedMax];  // the last block's copy of every block's value
-  if (threadIdx.x == 0) {
-    // written through and drained before counting in (reduced_arrive)
-    st_sc1(result + k, s);
-    if (result_host) result_host[k] = s;  // pinned host memory: not cached
-    last = reduced_arrive(S);
-  }
-  __syncthreads();
-  if (!last || threadIdx.x >= 64) return;
-  reduced_collect(S, result, vals, int(gridDim.x));
-  ctl_run(S, H, vals, nullptr, prm, status, t, P);
+  if (!reduce_to_last_wave(partial, nblk, result, result_host, S, t, P, R, vals)) return;
+  ctl_run(S, H, vals, nullptr, prm, status, t, P, R);
 }
 
 // Row slabs over the peer-memory communicator: the reduction, the all-reduce of its nval sums
@@ -125,24 +142,12 @@ __global__ void __launch_bounds__(RB) arn_reduce_allreduce_ctl_kernel(
     atomicMax(&g_ctl_tl, e);
   }
 #endif
-  // the control's loads (first wave of every block), in flight during the reduction (they
-  // lengthen it by ~1 us, but issued after it they cost more: profiles/r06_short_slab.md 9)
   CtlPre P;
-  if (threadIdx.x < 64) ctl_load(S, t, P);
-  const int k = blockIdx.x;
-  const double s = reduce_column<RB>(partial + int64_t(k) * nblk, nblk, true);
-  __shared__ bool last;
+  GramRegs R;
   __shared__ double vals[kRedMax];  // the last block's copy of every block's value
-  if (threadIdx.x == 0) {
-    st_sc1(result + k, s);
-    last = reduced_arrive(S);
-  }
-  __syncthreads();
-  if (!last || threadIdx.x >= 64) return;
-  CTL_STAMP(p_last);
-  const int n = int(gridDim.x);
-  reduced_collect(S, result, vals, n);
+  if (!reduce_to_last_wave(partial, nblk, result, nullptr, S, t, P, R, vals)) return;
   CTL_STAMP(p_coll);
+  const int n = int(gridDim.x);
   if (!peer_allreduce_wave_wt(pa, vals, n, n)) {
     if (threadIdx.x == 0) prm[kArnMaxNV + 3] = 1.0;  // the queued fused step does nothing
     return;
@@ -152,11 +157,12 @@ __global__ void __launch_bounds__(RB) arn_reduce_allreduce_ctl_kernel(
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
   CTL_STAMP(p_ar);
   for (int i = int(threadIdx.x); i < n; i += 64) result[i] = vals[i];
-  ctl_run(S, H, vals, result_host, prm, status, t, P);
+  ctl_run(S, H, vals, result_host, prm, status, t, P, R);
 #ifdef ARN_CTL_PROBE
   CTL_STAMP(p_end);
   if (threadIdx.x == 0) {
     const unsigned long long t0 = atomicAdd(&g_ctl_t0, 0ull), tl = atomicAdd(&g_ctl_tl, 0ull);
+    const unsigned long long p_last = g_ctl_last;
     atomicAdd(&g_ctl_probe[0], 1ull);
     atomicAdd(&g_ctl_probe[1], p_last - t0);
     atomicAdd(&g_ctl_probe[2], p_coll - p_last);

@@ -373,6 +373,73 @@ int nk_debug_mailbox(int64_t* counts, int32_t reset) {
   return rc == 0 ? NK_OK : (rc == -1 ? NK_EINVAL : NK_EHIP);
 }
 
+// One control step on a synthetic state, through the solver's own launches and with its kinds of
+// memory (NewtonKrylov's constructor): device state, pinned mirror and status, device parameters.
+int nk_debug_ctl_step(int32_t form, int32_t t, const int32_t* ints, const double* scal,
+                      const double* sig, const double* h, const double* cs, const double* sn,
+                      const double* gram, const double* red, void* state_out, void* mirror_out,
+                      double* prm_out, uint32_t* status_out) {
+  if (!state_out) return int(sizeof(ArnCtlState));
+  if ((form != 0 && form != 1) || t < 1 || t + 1 > kArnMaxNV || !ints || !scal || !sig || !h ||
+      !cs || !sn || !gram || !red || !mirror_out || !prm_out || !status_out)
+    return NK_EINVAL;
+  const int nval = 2 * (t + 1) + 1;
+  ArnCtlState *hS = nullptr, *dS = nullptr;
+  uint32_t* status = nullptr;
+  double *prm = nullptr, *dred = nullptr;  // dred: red, then the reducing launch's result
+  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&hS), sizeof(ArnCtlState), 0);
+  if (e == hipSuccess)
+    e = hipHostMalloc(reinterpret_cast<void**>(&status), sizeof(uint32_t) * (kMaxVec + 2), 0);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dS), sizeof(ArnCtlState));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&prm), sizeof(double) * kCtlPrm);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dred), sizeof(double) * 2 * nval);
+  if (e == hipSuccess) {
+    std::memset(hS, 0, sizeof(ArnCtlState));
+    std::memset(status, 0, sizeof(uint32_t) * (kMaxVec + 2));
+    ArnCtlState& S = *hS;
+    S.j = ints[0];
+    S.hn_pending = ints[1];
+    S.m = ints[2];
+    S.nv_max = ints[3];
+    S.halt = ints[4];
+    S.steps = ints[5];
+    S.wnorm[t - 1] = scal[0];
+    S.gv[t - 1] = scal[1];
+    S.sig_est[t] = scal[2];
+    S.ptol = scal[3];
+    S.omega = scal[4];
+    S.lag_ratio2 = scal[5];
+    for (int i = 0; i <= t; ++i) S.sig[i] = sig[i];
+    for (int i = 0; i < t; ++i) {
+      S.h[i] = h[i];
+      S.cs[i] = cs[i];
+      S.sn[i] = sn[i];
+      for (int k = 0; k < i; ++k) S.gram[i][k] = gram[i * t + k];
+    }
+    e = hipMemcpy(dS, hS, sizeof(ArnCtlState), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMemset(prm, 0, sizeof(double) * kCtlPrm);
+  if (e == hipSuccess) e = hipMemcpy(dred, red, sizeof(double) * nval, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = form == 0 ? arn_ctl_launch(dS, hS, dred, nullptr, prm, status, t, nullptr)
+                  : arn_reduce_ctl_launch(dred, 1, nval, dred + nval, nullptr, dS, hS, prm, status,
+                                          t, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(state_out, dS, sizeof(ArnCtlState), hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    e = hipMemcpy(prm_out, prm, sizeof(double) * kCtlPrm, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) {
+    std::memcpy(mirror_out, hS, sizeof(ArnCtlState));
+    *status_out = status[t];
+  }
+  if (hS) (void)hipHostFree(hS);
+  if (status) (void)hipHostFree(status);
+  (void)hipFree(dS);
+  (void)hipFree(prm);
+  (void)hipFree(dred);
+  return hip_rc(e);
+}
+
 // ------------------------------------------------------------------------------ comms
 int nk_comm_unique_id_bytes(void) { return comm_unique_id_bytes(); }
 int nk_comm_get_unique_id(void* out) { return out ? comm_get_unique_id(out) : NK_EINVAL; }
