@@ -272,10 +272,21 @@ __device__ __forceinline__ double dpp_down(double x) {
   return __builtin_bit_cast(double, r);
 }
 
-// u = v (or z) at element o of the grid, summed in the fused kernel's order -- for the pair
-// layout (h0 = 0) entries 0, 2, 4, .. of [V_0 .. V_{nv-1}, w] in one partial, 1, 3, 5, .. in the
-// other, then their sum; for the wide layout (h0 = nv + 1) all entries in order -- so an edge row
-// sent to a neighbour equals the row its owner computes.  Every entry load is in flight at once.
+// The order of the update sum over the entries [V_0 .. V_{nv-1}, w], for every place that forms
+// u outside the march's own registers (edge rows sent to a neighbour, pushed halo rows, a mailbox
+// pair recomputed by its consumer): entry e goes into the first of two partials when
+// UPD_FIRST(h0, e), else into the second, and the sum is first + second.  h0 is the layout's
+// split point (split_point): for the pair layout (0) entries 0, 2, 4, .. in one partial and
+// 1, 3, 5, .. in the other, as its two halves sum them; for the wide layout (nv + 1) all entries
+// in order.  So such a value equals, bit for bit, the one the row's owner computes in push().
+// (a macro, not a function: behind a call, even a force-inlined constexpr one, the ten nv = 2
+// fused kernels compiled differently, profiles/arnoldi_one_body.md)
+#define UPD_FIRST(h0, e) (((h0) > 0) ? ((e) < (h0)) : (((e) & 1) == 0))
+constexpr int split_point(bool wide, int nv) { return wide ? nv + 1 : 0; }
+
+// u = v (or z) at element o of the grid, summed in the fused kernel's order (UPD_FIRST), so an
+// edge row sent to a neighbour equals the row its owner computes.  Every entry load is in flight
+// at once.
 template <int NV>
 __device__ __forceinline__ double edge_u(const ArnoldiArgs& A, int64_t o, int h0, double a_tau) {
   if (A.z) return A.z[o];
@@ -289,7 +300,7 @@ __device__ __forceinline__ double edge_u(const ArnoldiArgs& A, int64_t o, int h0
   double p0 = 0.0, p1 = 0.0;
 #pragma unroll
   for (int e = 0; e < NE; ++e) {
-    if ((h0 > 0) ? (e < h0) : ((e & 1) == 0))
+    if (UPD_FIRST(h0, e))
       p0 = __builtin_fma(cf[e], x[e], p0);
     else
       p1 = __builtin_fma(cf[e], x[e], p1);
@@ -443,7 +454,7 @@ __device__ __forceinline__ void slab_push_prologue(const ArnoldiArgs& A, bool fi
 #pragma unroll
           for (int e = 0; e < NE; ++e) {
             const double cf = (e < NV) ? cst[e] : a_tau;
-            if ((h0 > 0) ? (e < h0) : ((e & 1) == 0))
+            if (UPD_FIRST(h0, e))
               p0 = __builtin_fma(cf, x[k][e], p0);
             else
               p1 = __builtin_fma(cf, x[k][e], p1);
@@ -694,6 +705,7 @@ __global__ void __launch_bounds__(64 * WB) arnoldi_kernel(const ArnoldiArgs A) {
   constexpr int NI = (NE + 1) / 2;         // 16-B loads per row and lane
   constexpr int NB = (NV + 1) / 2;         // loads holding basis entries
   constexpr int EX = NV + 1, EZ = NV + 2;  // entries of x0, z
+  constexpr int kH0 = split_point(false, NV);  // the update sum's split (UPD_FIRST)
   // lag rows r, r+1 of this lane's basis entries and of x0, for row r's dot products / stencil
   __shared__ dv2 lag[WB][2][NB + 1][64];
   // per row (parity slot): u on columns 0, 1, 62, 63 of every wave; the waves' partial sums of v
@@ -859,6 +871,8 @@ __global__ void __launch_bounds__(64 * WB) arnoldi_kernel(const ArnoldiArgs A) {
   };
   auto cfd = [&](int e) -> double { return e < NV ? arn_c(A, e) : (e == NV ? a_tau : 0.0); };
   auto recompute = [&](ix_t t) -> dv2 {
+    // (two entries a turn into two unconditional partials: this layout's order)
+    static_assert(UPD_FIRST(kH0, 0) && !UPD_FIRST(kH0, 1), "recompute() sums even and odd apart");
     const ix_t o2 = CI(wrap(t) * nx + fcol, nelem - 1);
     double p0x = 0.0, p0y = 0.0, p1x = 0.0, p1y = 0.0;
 #pragma unroll 1
@@ -1136,9 +1150,9 @@ __global__ void __launch_bounds__(64 * WB) arnoldi_kernel(const ArnoldiArgs A) {
   // halo rows it reads itself -- the same bits from every band -- and fences the edge rows it
   // pushes (a band ending at ny - 1 pushes row ny - 2)
   const bool top = r0 < 2, bot = r1 + 2 > ny;
-  if (A.x.me) slab_x_exchange<NV>(A, band, B0, BW, 0, a_tau, top, bot);  // uniform per block
+  if (A.x.me) slab_x_exchange<NV>(A, band, B0, BW, kH0, a_tau, top, bot);  // uniform per block
   const bool edge_band = A.hs_ld > 0 && (top || bot);
-  if (edge_band) slab_push_prologue<NV>(A, top, bot, B0, BW, 0, cst, a_tau);  // uniform per block
+  if (edge_band) slab_push_prologue<NV>(A, top, bot, B0, BW, kH0, cst, a_tau);  // uniform per block
   if (nrows > 0) {
     // prologue (logical rows, march order): rows -2, -1 (band halo) and 0, 1 enter the window
     // (0, 1 also the LDS lag); rows 2 .. 1+PF go in flight.  Row t >= 2 uses register slot
@@ -1240,7 +1254,7 @@ __global__ void __launch_bounds__(64 * WB) arnoldi_kernel(const ArnoldiArgs A) {
 constexpr int kWW = 128;       // columns per wave
 constexpr int kWideMaxNV = 18;  // LDS: 2 rows x (nv + 1) x 4 waves x 1 KB <= 152 KB
 
-template <int NV, bool EXT, int PF, bool ALT, int W, bool MB>
+template <int NV, bool EXT, int PF, bool ALT, int W>
 __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs A) {
   const double a_tau = arn_tau(A), a_alpha = arn_alpha(A), a_sc = arn_sc(A);
   double cst[NV];  // update coefficients, loaded together (independent loads, one wait)
@@ -1250,6 +1264,7 @@ __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs 
   constexpr int RR = PF + 1;
   constexpr int NE = NV + 2 + (EXT ? 1 : 0);  // [V_0 .. V_{NV-1}, w, x0, (z)]
   constexpr int EX = NV + 1, EZ = NV + 2;
+  constexpr int kH0 = split_point(true, NV);  // the update sum's split (UPD_FIRST)
   static_assert(NV + 1 <= 16 * W, "one packed halo load per row");
   __shared__ dv2 lag[W][2][NV + 1][64];  // basis rows r, r+1 and x0 (slot NV)
   __shared__ double edge[2][W][4];
@@ -1344,61 +1359,7 @@ __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs 
     return slab && (qc < 0 || qc >= ny);
   };
 
-  // mailbox, as in arnoldi_kernel: wave 0's lane 0 holds the first column pair and needs the
-  // left halo pair, wave W-1's lane 63 the last pair and the right halo pair
   constexpr int BW = W * kWW;
-  constexpr bool mb = MB && !EXT;
-  const ix_t mbT = A.RY + 8;
-  const __amdgpu_buffer_rsrc_t rmb = rsrc(A.mb, mb ? A.mb_cap : 0);
-  const uint64_t tag = A.mb_tag;
-  const bool needL = mb && wid == 0 && lane == 0, needR = mb && wid == W - 1 && lane == 63;
-  const ix_t Lnb = band * ngroups + (needL ? (grp + ngroups - 1) % ngroups : (grp + 1) % ngroups);
-  const int nside = needL ? 1 : 0;
-  const bool prod = needL || needR;
-  const int pside = needL ? 0 : 1;
-  const ix_t fcol = needL ? (B0 - 2 + nx) % nx : (B0 + BW) % nx;
-  bool mb_dead = A.mb_recompute;
-  auto mb_need = [&](ix_t t) -> bool { return (needL || needR) && !halo_row(t); };
-  auto poll = [&](ix_t t, u32x4* a, u32x4* b) {
-    const bool on = mb_need(t) && !mb_dead;
-    const uint32_t o = mb_off(Lnb, mbT, t + 2, nside, 0);
-    ARN_CHK(!on || (t + 2 >= 0 && t + 2 < mbT && int64_t(o) + 32 <= A.mb_cap * 8));
-    *a = __builtin_amdgcn_raw_buffer_load_b128(rmb, on ? o : kOOB, 0, kMBCoh);
-    *b = __builtin_amdgcn_raw_buffer_load_b128(rmb, on ? o + 16 : kOOB, 0, kMBCoh);
-  };
-  auto recompute = [&](ix_t t) -> dv2 {  // push()'s update sum, entry order (rolled loop)
-    const ix_t o2 = CI(wrap(t) * nx + fcol, nelem - 1);
-    dv2 v{0.0, 0.0};
-#pragma unroll 1
-    for (int e = 0; e <= NV; ++e) {
-      const dv2 x = gld2<false>((e < NV ? A.V[e] : A.w) + o2);
-      const double cf = e < NV ? arn_c(A, e) : a_tau;
-      v.x = __builtin_fma(cf, x.x, v.x);
-      v.y = __builtin_fma(cf, x.y, v.y);
-    }
-    return v;
-  };
-  auto mb_halo = [&](ix_t t, u32x4 a, u32x4 b) -> dv2 {
-    const bool need = mb_need(t);
-    bool ok = !need || (!mb_dead && mb_tag_ok(a, tag) && mb_tag_ok(b, tag));
-    dv2 h{mb_val(a), mb_val(b)};
-    if (!ok) {
-      const uint32_t o = mb_off(Lnb, mbT, t + 2, nside, 0);
-      for (int n = 0; n < kMBSpin && !mb_dead && !ok; ++n) {
-        __builtin_amdgcn_s_sleep(2);
-        a = __builtin_amdgcn_raw_buffer_load_b128(rmb, o, 0, kMBCoh);
-        b = __builtin_amdgcn_raw_buffer_load_b128(rmb, o + 16, 0, kMBCoh);
-        ok = mb_tag_ok(a, tag) && mb_tag_ok(b, tag);
-      }
-      if (ok) {
-        h = dv2{mb_val(a), mb_val(b)};
-      } else {
-        mb_dead = true;
-        h = recompute(t);
-      }
-    }
-    return need ? h : dv2{-0.0, -0.0};
-  };
 
   struct Slot {
     dv2 e[NE];
@@ -1419,12 +1380,12 @@ __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs 
       s.e[e] = gld2<decltype(pol)::value>(a);
     }
     const ix_t ho = CI(qq * nx + hcol, nelem);
-    if constexpr (!EXT && !mb) {
+    if constexpr (!EXT) {
       const ix_t eo = CI(useE ? ((((hh < 2) ? bL : bR) * ny + qq) << 2) + hh : 0, eelem);
       s.hv = gld(useE ? hE + eo : hp + ho);
     }
     const ix_t hyo = CI(hq * yld + hcol, 4 * yld);
-    s.hx = gld((hrow && lane < 4) ? yhb + hyo : (mb ? A.x0 : hxp + ho));
+    s.hx = gld((hrow && lane < 4) ? yhb + hyo : hxp + ho);
     s.own = !hrow;
   };
   auto stash = [&](const Slot& s, const dv2& g, ix_t t) {
@@ -1454,17 +1415,7 @@ __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs 
     else
       u = s.own ? v : xe;
     const int slot = int(t & 1);
-    {  // mailbox: publish u on this block's first / last column pair
-      if constexpr (mb) {
-        const bool pq = prod && s.own;
-        const uint32_t po = mb_off(L, mbT, t + 2, pside, 0);
-        ARN_CHK(!pq || (t + 2 >= 0 && t + 2 < mbT && int64_t(po) + 32 <= A.mb_cap * 8));
-        __builtin_amdgcn_raw_buffer_store_b128(mb_rec(u.x, tag), rmb, pq ? po : kOOB, 0, kMBCoh);
-        __builtin_amdgcn_raw_buffer_store_b128(mb_rec(u.y, tag), rmb, pq ? po + 16 : kOOB, 0,
-                                               kMBCoh);
-      }
-    }
-    if constexpr (!EXT && !mb) {
+    if constexpr (!EXT) {
       double hs = hcf * s.hv;
       hs += dpp_row_shr(hs, 4);
       hs += dpp_row_shr(hs, 8);
@@ -1483,11 +1434,10 @@ __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    double hz = -0.0;  // mailbox: added by fixup()
+    double hz = 0.0;
     if constexpr (EXT) {
       hz = __shfl(s.hx, hh + 4, 64);
-    } else if constexpr (!mb) {
-      hz = 0.0;
+    } else {
 #pragma unroll
       for (int w = 0; w < W; ++w) hz += hpart[slot][w][hh];
     }
@@ -1575,17 +1525,11 @@ __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs 
     h2w[1] = h2w[2];
     h2w[2] = h2;
   };
-  auto fixup = [&](dv2& hq, dv2& h2q, const dv2& h) {  // as in arnoldi_kernel
-    hq.x = hq.x + (needL ? h.y : -0.0);
-    hq.y = hq.y + (needR ? h.x : -0.0);
-    h2q.x = h2q.x + h.x;
-    h2q.y = h2q.y + h.y;
-  };
 
   const bool top = r0 < 2, bot = r1 + 2 > ny;  // as in arnoldi_kernel
-  if (A.x.me) slab_x_exchange<NV>(A, band, B0, BW, NV + 1, a_tau, top, bot);  // uniform per block
+  if (A.x.me) slab_x_exchange<NV>(A, band, B0, BW, kH0, a_tau, top, bot);  // uniform per block
   const bool edge_band = A.hs_ld > 0 && (top || bot);
-  if (edge_band) slab_push_prologue<NV>(A, top, bot, B0, BW, NV + 1, cst, a_tau);
+  if (edge_band) slab_push_prologue<NV>(A, top, bot, B0, BW, kH0, cst, a_tau);
   if (nrows > 0) {  // logical rows, march order (see arnoldi_kernel)
     Slot S[RR];
     {
@@ -1603,24 +1547,12 @@ __global__ void __launch_bounds__(64 * W) arnoldi_wide_kernel(const ArnoldiArgs 
       push_h2(P[1], 1);
       stash(P[1], gq, 1);
     }
-    {
-      if constexpr (mb) {
-        u32x4 a0, b0, a1, b1;
-        poll(-1, &a0, &b0);
-        poll(0, &a1, &b1);
-        fixup(hw[2], h2w[0], mb_halo(-1, a0, b0));
-        fixup(hw[3], h2w[1], mb_halo(0, a1, b1));
-      }
-    }
     for (ix_t t0 = 0; t0 < nrows; t0 += RR) {  // no branch inside a group (see arnoldi_kernel)
 #pragma unroll
       for (int k = 0; k < RR; ++k) {
         const ix_t t = t0 + k;
-        u32x4 ma, mb2;
-        if constexpr (mb) poll(t + 1, &ma, &mb2);
         load(S[(k + PF) % RR], t + 2 + PF, NTc{});
         push_h2(S[k], t + 2);
-        if constexpr (mb) fixup(hw[3], h2w[1], mb_halo(t + 1, ma, mb2));
         centre(t);
         stash(S[k], gq, t + 2);
       }
@@ -1804,16 +1736,15 @@ hipError_t launch_t(const ArnoldiArgs& A, hipStream_t s, int64_t* nwaves) {
 constexpr int kWideW = 4;  // waves per block of the wide layout (512 columns)
 template <int NV, bool EXT, int PF>
 hipError_t launch_wide(const ArnoldiArgs& A, hipStream_t s, int64_t* nwaves) {
-  // no mailbox instantiation: with 512-column blocks the packed halo is the cheaper one
-  // (4096^2, one box: n4 0.63 vs 0.55, n12 0.64 vs 0.63, n18 0.62 vs 0.57 of 8 TB/s)
-  // (the wide kernel keeps a mailbox instantiation parameter, MB; it measured no gain with 2- or
-  // 4-wave blocks, profiles/r02_arnoldi_ab.md, and is not instantiated)
-  using K = decltype(&arnoldi_wide_kernel<NV, EXT, PF, false, kWideW, false>);
+  // no mailbox in the wide kernel: with 512-column blocks the packed halo is the cheaper one
+  // (4096^2, one box: n4 0.63 vs 0.55, n12 0.64 vs 0.63, n18 0.62 vs 0.57 of 8 TB/s; no gain
+  // with 2- or 4-wave blocks either, profiles/r02_arnoldi_ab.md)
+  using K = decltype(&arnoldi_wide_kernel<NV, EXT, PF, false, kWideW>);
   static const Kerns<K> KS = [] {
-    Kerns<K> k{arnoldi_wide_kernel<NV, EXT, PF, false, kWideW, false>,
-               arnoldi_wide_kernel<NV, EXT, PF, false, kWideW, false>,
-               arnoldi_wide_kernel<NV, EXT, PF, true, kWideW, false>,
-               arnoldi_wide_kernel<NV, EXT, PF, true, kWideW, false>, {}, {}, {}, {}};
+    Kerns<K> k{arnoldi_wide_kernel<NV, EXT, PF, false, kWideW>,
+               arnoldi_wide_kernel<NV, EXT, PF, false, kWideW>,
+               arnoldi_wide_kernel<NV, EXT, PF, true, kWideW>,
+               arnoldi_wide_kernel<NV, EXT, PF, true, kWideW>, {}, {}, {}, {}};
     k.occ = k.occ_mb = query_occ(k.kern, 64 * kWideW);
     k.occ_a = k.occ_mb_a = query_occ(k.kern_a, 64 * kWideW);
     return k;
@@ -1865,10 +1796,8 @@ hipError_t launch_e(const ArnoldiArgs& A, hipStream_t s, int64_t* nwaves) {
 }
 
 // u (= v, or z) on the edge rows 0, 1, ny-2, ny-1 of a slab (grid: column blocks x 4 rows).
-// The update sum runs in the fused kernel's order -- for the pair layout (h0 = 0) entries 0, 2,
-// 4, .. of [V_0 .. V_{nv-1}, w] in one partial, 1, 3, 5, .. in the other, then their sum; for the
-// wide layout (h0 = nv + 1) all entries in order -- so a halo row
-// equals the row its owner computes.
+// The update sum runs in the fused kernel's order (UPD_FIRST with h0 = edge_split_point(nv)),
+// so a halo row equals the row its owner computes.
 // PEER (row slabs over the peer-memory communicator): the kernel also performs the halo exchange
 // -- it writes its rows straight into the neighbours' staging rows (peer_dev.h), publishes,
 // waits for its own and copies them into yh (lo = rows 0, 1, hi = rows 2, 3) -- one launch
@@ -1950,10 +1879,7 @@ hipError_t edge_gather_launch(const double* v, double* E, int64_t ny, int64_t nx
 
 // where the layout of basis length nv splits its update sum in two (0: the pair layout's even /
 // odd entries; nv + 1: the wide layout's whole sum in entry order)
-int edge_split_point(int nv) {
-  if (arnoldi_wide(nv)) return nv + 1;
-  return 0;
-}
+int edge_split_point(int nv) { return split_point(arnoldi_wide(nv), nv); }
 
 hipError_t arnoldi_edge_launch(const ArnoldiArgs& A, double* y4, hipStream_t s) {
   if (A.ny < 4 || A.nx < 1 || !y4) return hipErrorInvalidValue;

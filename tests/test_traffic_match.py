@@ -29,7 +29,7 @@ def _csv(path, rows):
 
 def test_per_dispatch_ratios(tmp_path):
     fused = "void nk::(anonymous namespace)::arnoldi_kernel<24, false, 1, true, true, 2>(nk::ArnoldiArgs)"
-    wide = "void nk::(anonymous namespace)::arnoldi_wide_kernel<8, false, 2, true, 4, false>(nk::ArnoldiArgs)"
+    wide = "void nk::(anonymous namespace)::arnoldi_wide_kernel<8, false, 2, true, 4>(nk::ArnoldiArgs)"
     jvp = "void nk::(anonymous namespace)::march_kernel<(nk::SMode)5, 128, 1>(nk::StencilArgs, int, int, int)"
     other = "void at::native::vectorized_elementwise_kernel<4>(int)"  # not the solver's: ignored
     fetch = _csv(tmp_path / "f.csv", [
