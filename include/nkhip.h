@@ -189,6 +189,14 @@ int nk_debug_bounds(int64_t* violations, int32_t* first_line, int32_t reset);
  * recomputed after kMBSpin polls.  NK_EINVAL from the other builds.  Diagnostic only: no
  * reference interface. */
 int nk_debug_mailbox(int64_t* counts, int32_t reset);
+/* The closing pass of an LGMRES cycle on caller vectors: one read of
+ * the m distinct device vectors P[i] (1 <= m <= 64, n >= 1 elements; host arrays of pointers and
+ * coefficients) gives A = sum cA[i] P[i], B = sum cB[i] P[i] and *norm2 = sum_e (sum_i cN[i]
+ * P[i][e])^2, each sum over i in list order.  A != B; NK_EINVAL when a vector is listed twice.
+ * Synchronises `stream`.  Diagnostic only: no reference interface. */
+int nk_debug_close(const double* const* P_dev, const double* cN, const double* cA,
+                   const double* cB, int32_t m, int64_t n, double* A_dev, double* B_dev,
+                   double* norm2, void* stream);
 /* One step t (1 <= t <= 34) of the device-side Arnoldi control on a
  * synthetic loop state, through the solver's own launch of either form of the control -- form 0:
  * the control launch that stages the Gram rows through LDS (the code the fused launches' tail

@@ -373,6 +373,25 @@ int nk_debug_mailbox(int64_t* counts, int32_t reset) {
   return rc == 0 ? NK_OK : (rc == -1 ? NK_EINVAL : NK_EHIP);
 }
 
+int nk_debug_close(const double* const* P, const double* cN, const double* cA, const double* cB,
+                   int32_t m, int64_t n, double* A, double* B, double* norm2, void* stream) {
+  if (!P || !cN || !cA || !cB || !A || !B || A == B || !norm2 || m < 1 || m > kMaxVec || n < 1)
+    return NK_EINVAL;
+  CloseList L;
+  for (int i = 0; i < m; ++i) {
+    for (int k = 0; k < i; ++k)
+      if (P[k] == P[i]) return NK_EINVAL;  // the kernel's contract: distinct vectors
+    if (!P[i]) return NK_EINVAL;
+    L.p[i] = P[i];
+    L.cN[i] = cN[i];
+    L.cA[i] = cA[i];
+    L.cB[i] = cB[i];
+  }
+  return reduce_call(n, 1, 1, 1, norm2, S(stream), [&](double* part, int64_t* nb) {
+    return close_launch(A, B, L, m, n, part, S(stream), nb);
+  });
+}
+
 // One control step on a synthetic state, through the solver's own launches and with its kinds of
 // memory (NewtonKrylov's constructor): device state, pinned mirror and status, device parameters.
 int nk_debug_ctl_step(int32_t form, int32_t t, const int32_t* ints, const double* scal,

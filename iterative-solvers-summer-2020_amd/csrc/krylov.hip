@@ -4,7 +4,9 @@
 // (scipy/sparse/linalg/_isolve/_gcrotmk.py:104-143) with two fused passes per Arnoldi step:
 //   mdot  -- all inner products V^T w (and the new Gram row V^T v_j, and w.w) in ONE read of
 //            w and the basis, partial sums per block;
-//   combo -- w <- w - sum_i c_i v_i together with |w|^2 and max|w| in ONE read-modify-write.
+//   combo -- w <- w - sum_i c_i v_i together with |w|^2 and max|w| in ONE read-modify-write;
+//   close -- the last step of an LGMRES cycle: the two vectors dx is made of and |v_{j+1}|^2 in
+//            ONE read of the basis (combo_kernel<Close, ...>).
 // A block owns a contiguous 2048-element chunk (256 threads x 4 double2), keeps its chunk of w
 // in registers and streams the basis vectors through it; reductions are wave64 xor-shuffles, one
 // LDS round, then a deterministic second-stage kernel (fixed summation order, so a run is
@@ -235,6 +237,79 @@ __global__ void __launch_bounds__(BS) combo_kernel(double* out, const double* in
   }
 }
 
+// Closing pass of an LGMRES cycle (lgmres.cpp "Closing pass"): ONE read of np distinct vectors
+// gives A = sum cA_i p_i and B = sum cB_i p_i (the two vectors d = A + y_j B is made of once the
+// host has |v_{j+1}|) and the block partials of sum (sum cN_i p_i)^2 = |v_{j+1}|^2, with
+// combo_kernel's chunking, traversal and sum order: each of the three sums is one FMA chain over
+// the vectors in list order.  A zero coefficient is multiplied and added like any other (no
+// branch: a fixed order).  outA / outB may alias a p_i (each element is read before it is
+// written, by the same thread).  The tag keeps the kernel under combo_kernel's name.
+struct Close {};
+template <class Tag, bool VEC, bool NT, int UNR>
+__global__ void __launch_bounds__(BS) combo_kernel(double* outA, double* outB, CloseList P, int np,
+                                                   int64_t n, int cpb, double* partial, bool rev) {
+  const int64_t nblk = gridDim.x;
+  const int64_t bid = blockIdx.x;
+  double red[1] = {0.0};
+  const int64_t grp = rev ? nblk - 1 - bid : bid;  // see mdot_kernel
+  for (int cc = 0; cc < cpb; ++cc) {
+    const int64_t chunk = grp * cpb + cc;
+    if (chunk * kKrylovChunk >= n) break;  // uniform
+    const int64_t base = chunk * kKrylovChunk + 2 * int64_t(threadIdx.x);
+    double2 aN[PAIRS], aA[PAIRS], aB[PAIRS];
+#pragma unroll
+    for (int k = 0; k < PAIRS; ++k) aN[k] = aA[k] = aB[k] = make_double2(0.0, 0.0);
+    int i = 0;
+    for (; i + UNR <= np; i += UNR) {  // the sums stay in vector order
+      double2 pv[UNR][PAIRS];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+#pragma unroll
+        for (int k = 0; k < PAIRS; ++k) pv[u][k] = ld2s<VEC, NT>(P.p[i + u], base + k * 2 * BS, n);
+      }
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const double cn = P.cN[i + u], ca = P.cA[i + u], cb = P.cB[i + u];
+#pragma unroll
+        for (int k = 0; k < PAIRS; ++k) {
+          aN[k].x += cn * pv[u][k].x;
+          aN[k].y += cn * pv[u][k].y;
+          aA[k].x += ca * pv[u][k].x;
+          aA[k].y += ca * pv[u][k].y;
+          aB[k].x += cb * pv[u][k].x;
+          aB[k].y += cb * pv[u][k].y;
+        }
+      }
+    }
+    for (; i < np; ++i) {
+      const double* p = P.p[i];
+      const double cn = P.cN[i], ca = P.cA[i], cb = P.cB[i];
+      double2 pv[PAIRS];
+#pragma unroll
+      for (int k = 0; k < PAIRS; ++k) pv[k] = ld2s<VEC, NT>(p, base + k * 2 * BS, n);
+#pragma unroll
+      for (int k = 0; k < PAIRS; ++k) {
+        aN[k].x += cn * pv[k].x;
+        aN[k].y += cn * pv[k].y;
+        aA[k].x += ca * pv[k].x;
+        aA[k].y += ca * pv[k].y;
+        aB[k].x += cb * pv[k].x;
+        aB[k].y += cb * pv[k].y;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PAIRS; ++k) {
+      st2<VEC>(outA, base + k * 2 * BS, n, aA[k]);
+      st2<VEC>(outB, base + k * 2 * BS, n, aB[k]);
+      const int64_t e = base + k * 2 * BS;
+      if (e < n) red[0] += aN[k].x * aN[k].x;
+      if (e + 1 < n) red[0] += aN[k].y * aN[k].y;
+    }
+  }
+  const double v = block_reduce<1, 1, BS>(red);
+  if (threadIdx.x == 0) partial[grp] = v;
+}
+
 constexpr int RB = 1024;  // reduce_final block: <= 4 partials per thread at 4096 producer blocks
 
 __global__ void __launch_bounds__(RB) reduce_final_kernel(const double* partial, int64_t nblk,
@@ -405,6 +480,40 @@ hipError_t combo_prm_launch(double* out, const double* in, const double* prm, co
                             int np, int64_t n, hipStream_t s) {
   if (!prm || np > kArnMaxNV) return hipErrorInvalidValue;
   return combo_any(out, in, 0.0, P, np, n, nullptr, s, nullptr, prm, EdgeOut{});
+}
+
+hipError_t close_launch(double* outA, double* outB, const CloseList& P, int np, int64_t n,
+                        double* partial, hipStream_t s, int64_t* nblk) {
+  if (np < 1 || np > kMaxVec || !outA || !outB || outA == outB || !partial)
+    return hipErrorInvalidValue;
+  static const int target = env_int("NKHIP_COMBO_BLOCKS", 1 << 30);
+  int cpb = 0;
+  const int64_t nb = krylov_grid(n, &cpb, target);
+  if (nblk) *nblk = nb;
+  if (nb == 0) return hipSuccess;
+  bool vec = al16(outA) && al16(outB);
+  for (int i = 0; i < np; ++i) vec = vec && al16(P.p[i]);
+  const bool rev = traversal_reverse();
+  static const bool nt = env_int("NKHIP_NT", 1) != 0;
+  const dim3 grid{unsigned(nb)}, block{unsigned(BS)};
+  if (nb <= kSmallChunks) {  // small vectors: as combo_any
+    if (vec)
+      hipLaunchKernelGGL((combo_kernel<Close, true, false, 8>), grid, block, 0, s, outA, outB, P,
+                         np, n, cpb, partial, rev);
+    else
+      hipLaunchKernelGGL((combo_kernel<Close, false, false, 8>), grid, block, 0, s, outA, outB, P,
+                         np, n, cpb, partial, rev);
+  } else if (vec && nt) {
+    hipLaunchKernelGGL((combo_kernel<Close, true, true, 2>), grid, block, 0, s, outA, outB, P, np,
+                       n, cpb, partial, rev);
+  } else if (vec) {
+    hipLaunchKernelGGL((combo_kernel<Close, true, false, 2>), grid, block, 0, s, outA, outB, P, np,
+                       n, cpb, partial, rev);
+  } else {
+    hipLaunchKernelGGL((combo_kernel<Close, false, false, 2>), grid, block, 0, s, outA, outB, P,
+                       np, n, cpb, partial, rev);
+  }
+  return hipGetLastError();
 }
 
 hipError_t reduce_final_launch(const double* partial, int64_t nblk, int nsum, int nv,

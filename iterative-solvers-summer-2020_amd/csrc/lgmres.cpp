@@ -14,10 +14,28 @@
 //          was applied to a vector of norm 1 +- rounding, as in KrylovJacobian.matvec, so
 //          tau * w_{j+1} = J v_{j+1} with the exactly normalised v_{j+1}.
 // When |v_{j+1}| << |w_j| the estimate cancels (|v|/|w| < 1e-6): that step reduces the exact
-// norm before the JVP (its in-kernel scale), as does the last step.  When step j turns out to be
-// the last one, the JVP/multi-dot issued for j+1 are discarded (not counted).
+// norm before the JVP (its in-kernel scale).  When step j turns out to be the last one although
+// it was not predicted to be, the JVP/multi-dot issued for j+1 are discarded (not counted).
 // NKHIP_LAGNORM=0 disables the lagged norm (every step reduces |v_{j+1}| first); so does a
 // problem that must not evaluate a discarded JVP (a user callback: scipy's exact F-call count).
+//
+// Closing pass: once h_j is known, only hn = |v_{j+1}| of the Hessenberg QR is missing, and the
+// estimate above says whether step j will pass the residual test (or j + 1 = m ends the process
+// anyway).  Then no step j+1 is issued.  With R1 = the leading j x j block of R (final), the
+// solution of the small system is y_i = a_i - b_i y_j for i < j (a = R1^-1 gv, b = R1^-1
+// R[0..j-1][j], neither depends on hn), so dx = A + y_j B with A = sum_{i<j} a_i z_i and
+// B = z_j - sum_{i<j} b_i z_i (z's scales and |b| folded in).  One pass over the distinct
+// vectors among w, V_0..V_j and the z_i (krylov.hip close_launch) writes A and B and reduces the
+// exact |tau w - V h|^2; the host finishes step j with it and a two-vector combination forms dx:
+// about (j + 3) + 3 vector passes in place of the discarded fused step's (j + 5) and the
+// combination's (j + 2).  If the exact norm says "go on" after all, nothing was committed and
+// the step takes the exact-norm path below (one pass lost).  NKHIP_CLOSE=0 turns it off, =2
+// forces the prediction at the first step of every call (tests).  The pass is taken only where
+// the problem has a fused step for the basis length past j (has_fused(j + 1)), i.e. where the
+// launch it replaces is the bandwidth-bound fused one: it changes the rounding of hn and dx, and
+// on the unfused paths (odd grids, the analytic JVP, the moving-mesh problems) nothing was
+// measured that would pay for that -- tests/test_gpu_nk.py's large-amplitude 61 x 61 fixture
+// amplifies one ulp of dx to 1e-5 of the next direction through the FD quotient.
 //
 // Device-side control (device_steps, arnctl.hip): once a fused step applies J to the new basis
 // vector itself, the same per-step arithmetic runs in a one-wave kernel between the fused
@@ -58,6 +76,16 @@ bool lag_enabled() {
     return !(v && v[0] == '0');
   }();
   return on;
+}
+
+// NKHIP_CLOSE (read per call): 0 = no closing pass, 1 = on (default wherever the lagged norm
+// is), 2 = also force the prediction "last" at the first step of every call (tests: the
+// misprediction path)
+int close_mode_env() {
+  const char* v = std::getenv("NKHIP_CLOSE");
+  if (v && v[0] == '0') return 0;
+  if (v && v[0] == '2') return 2;
+  return 1;
 }
 }  // namespace
 
@@ -154,18 +182,30 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
   // Step i is complete once hn = |v_{i+1}| (raw) is known: Hessenberg column i, Givens update of
   // its QR (qr_insert, _gcrotmk.py:146-158), residual test (:165).  True when the process stops.
   // (arnctl.hip restates this for the device-side control.)
+  // Hessenberg column i = (h, hn) under the rotations of the earlier columns: hc[0..i-1] are the
+  // final R[0..i-1][i] (they do not depend on hn), hc[i], hc[i+1] the pair the new rotation takes
+  auto rotated = [&](int i, double hn, double* hc) {
+    for (int k = 0; k <= i; ++k) hc[k] = h[k];
+    hc[i + 1] = hn;
+    for (int k = 0; k < i; ++k) {
+      const double t = S.cs[k] * hc[k] + S.sn[k] * hc[k + 1];
+      hc[k + 1] = -S.sn[k] * hc[k] + S.cs[k] * hc[k + 1];
+      hc[k] = t;
+    }
+  };
+  // finish(i, hn)'s verdict without committing anything (the closing pass: prediction and check)
+  auto would_stop = [&](int i, double hn) -> bool {
+    double hc[kMaxVec + 2], c, s;
+    rotated(i, hn, hc);
+    detail::givens(hc[i], hc[i + 1], &c, &s);
+    return std::fabs(-s * S.gv[i]) < ptol || !(hn > kEps * wnorm[i]);
+  };
   auto finish = [&](int i, double hn) -> bool {
-    for (int k = 0; k <= i; ++k) hcur[k] = h[k];
-    hcur[i + 1] = hn;
+    rotated(i, hn, hcur);
     const double alpha = 1.0 / hn;
     sig[i + 1] = std::isfinite(alpha) ? alpha : 1.0;  // scipy leaves w unscaled then
     rn[i + 1] = hn;
     const bool breakdown = !(hn > kEps * wnorm[i]);
-    for (int k = 0; k < i; ++k) {
-      const double t = S.cs[k] * hcur[k] + S.sn[k] * hcur[k + 1];
-      hcur[k + 1] = -S.sn[k] * hcur[k] + S.cs[k] * hcur[k + 1];
-      hcur[k] = t;
-    }
     detail::givens(hcur[i], hcur[i + 1], &S.cs[i], &S.sn[i]);
     hcur[i] = S.cs[i] * hcur[i] + S.sn[i] * hcur[i + 1];
     for (int k = 0; k <= i; ++k) S.R[k][i] = hcur[k];
@@ -190,6 +230,8 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
   if (!rc) rc = E_.sync();
   if (rc) return rc;
   int j = 0, last = 0;
+  int close_mode = lag ? close_mode_env() : 0;  // 0 off, 1 on, 2 forced at the first step
+  bool closed = false;  // the cycle ended in a closing pass: A in Sv_, B in V_[last + 2]
   bool hn_pending = false;  // step j-1 still waits for |v_j| (Gram diagonal of multi-dot j)
   for (;;) {
     // -- results of the multi-dot of step j
@@ -230,8 +272,87 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
     const bool more = j + 1 < m;
     const bool next_is_v = more && (j + 1 > n_o);  // step j+1 applies J to v_{j+1} itself
     const double est = ww - hh;                    // |v_{j+1}|^2 = |w|^2 - |h|^2
-    const bool lag_step = more && lag && (!next_is_v || est > kLagMinRatio2 * ww);
     int64_t nblk = 0;
+    // -- closing pass: step j is predicted to end the process
+    //    (only where the step past j would be a fused launch: see the header)
+    bool predicted = false;
+    if (close_mode && P_.has_fused(j + 1) && j + 2 < int(V_.size())) {
+      const double hn_est = std::sqrt(est);
+      if (close_mode == 2) {  // forced once (tests: the misprediction below)
+        predicted = true;
+        close_mode = 1;
+      } else if (hn_est > kEps * wnorm[j]) {  // (a predicted breakdown takes the exact-norm step)
+        predicted = !more || (est > kLagMinRatio2 * ww && would_stop(j, hn_est));
+      }
+    }
+    if (predicted) {
+      // y_i = a_i - b_i y_j (i < j) by back substitution on the leading j x j block of R, whose
+      // columns and right-hand side are final: a = R1^-1 gv, b = R1^-1 R[0..j-1][j]
+      double hc[kMaxVec + 2], a[kMaxVec + 1], b[kMaxVec + 1];
+      rotated(j, 0.0, hc);
+      if (j > 0 && !detail::lstsq_upper_direct(S.R, j)) {
+        close_mode = 0;  // lstsq's singular fallback is not linear in y_j: not in this call
+        predicted = false;
+      }
+      for (int i = j - 1; predicted && i >= 0; --i) {
+        double accA = S.gv[i], accB = hc[i];
+        for (int k = i + 1; k < j; ++k) {
+          accA -= S.R[i][k] * a[k];
+          accB -= S.R[i][k] * b[k];
+        }
+        a[i] = accA / S.R[i][i];
+        b[i] = accB / S.R[i][i];
+      }
+      // the distinct vectors: w and the basis (the norm's sum in the update's order), then the
+      // inputs z_i that are not basis vectors (the augmentation vectors)
+      CloseList C;
+      int nc = 0;
+      auto entry = [&](const double* p) -> int {
+        for (int q = 0; q < nc; ++q)
+          if (C.p[q] == p) return q;
+        if (nc == kMaxVec) return -1;
+        C.p[nc] = p;
+        C.cN[nc] = C.cA[nc] = C.cB[nc] = 0.0;
+        return nc++;
+      };
+      if (predicted) {
+        C.cN[entry(w)] = tau;
+        for (int i = 0; i <= j; ++i) C.cN[entry(V_[i])] = U.c[i];
+        for (int i = 0; i <= j; ++i) {
+          const int q = entry(zp_[i]);
+          if (q < 0) {  // more distinct vectors than one launch takes
+            predicted = false;
+            break;
+          }
+          if (i < j) {
+            C.cA[q] += b_norm * a[i] * zs_[i];
+            C.cB[q] -= b[i] * zs_[i];
+          } else {
+            C.cB[q] += zs_[j];
+          }
+        }
+      }
+      if (predicted) {
+        // A, B into the two vectors a speculative fused step would write
+        rc = E_.launch(K_COMBO, 8.0 * n * (nc + 2), [&] {
+          return close_launch(Sv_, V_[j + 2], C, nc, n, E_.partial(), E_.s, &nblk);
+        });
+        if (rc) return rc;
+        double v2 = 0.0;
+        rc = E_.reduce(nblk, 1, 1, &v2);  // |v_{j+1}|^2: one reduction, one all-reduce
+        if (rc) return rc;
+        const double hn = std::sqrt(v2);
+        if (!more || would_stop(j, hn)) {
+          finish(j, hn);
+          last = j;
+          closed = true;
+          break;
+        }
+        // mispredicted: the process goes on with the exact-norm step below (one extra pass)
+      }
+    }
+    const bool lag_step =
+        more && lag && !predicted && (!next_is_v || est > kLagMinRatio2 * ww);
     if (lag_step && P_.has_fused(j + 1)) {
       // -- fused: v_{j+1} = tau w - V h, JVP_{j+1} and multi-dot_{j+1} in one pass over V
       //    (arnoldi.hip).  v_{j+1} lands in the spare vector, which then takes V_[j+1]'s place.
@@ -372,9 +493,19 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
   //    combination reads each element before writing it, so in-place is safe)
   const int slot = (o_.outer_k > 0 && ocount_ < o_.outer_k) ? (ohead_ + ocount_) % K : ohead_;
   VecList Z;
-  for (int i = 0; i <= j; ++i) {
-    Z.p[i] = zp_[i];
-    Z.c[i] = y[i] * zs_[i];
+  int nz = j + 1;
+  if (closed && detail::lstsq_upper_direct(S.R, j + 1)) {
+    // d = A + y_j B: y_i = a_i - b_i y_j is what lstsq's back substitution computed
+    nz = 2;
+    Z.p[0] = Sv_;
+    Z.c[0] = 1.0;
+    Z.p[1] = V_[j + 2];
+    Z.c[1] = y[j];
+  } else {
+    for (int i = 0; i <= j; ++i) {
+      Z.p[i] = zp_[i];
+      Z.c[i] = y[i] * zs_[i];
+    }
   }
   int64_t nblk = 0;
   double* d = outer_[slot];
@@ -382,8 +513,8 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
   // its edge array (written by the combination), and on pushed-halo slabs its edge rows, before
   // the all-reduce below
   const EdgeOut eo = P_.edge_out(d);
-  rc = E_.launch(K_COMBO, 8.0 * n * (j + 2), [&] {
-    return combo_launch(d, nullptr, 0.0, Z, j + 1, n, E_.partial(), E_.s, &nblk, eo);
+  rc = E_.launch(K_COMBO, 8.0 * n * (nz + 1), [&] {
+    return combo_launch(d, nullptr, 0.0, Z, nz, n, E_.partial(), E_.s, &nblk, eo);
   });
   if (!rc) rc = P_.publish_edges(d, eo.E != nullptr);
   if (rc) return rc;

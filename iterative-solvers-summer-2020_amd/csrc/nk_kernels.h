@@ -149,6 +149,16 @@ hipError_t combo_launch(double* out, const double* in, double cin, const VecList
 // coefficients the control kernel wrote); nothing when the step was handed back (prm halt entry).
 hipError_t combo_prm_launch(double* out, const double* in, const double* prm, const VecList& P,
                             int np, int64_t n, hipStream_t s);
+// Closing pass of an LGMRES cycle: one read of the np DISTINCT vectors p_i (1 <= np <= kMaxVec)
+// gives outA = sum cA_i p_i, outB = sum cB_i p_i and partial[0..*nblk) = the block sums of
+// (sum cN_i p_i)^2; each sum runs over the list in order, as combo_launch's does.  outA != outB;
+// either may alias a p_i.  8 (np + 2) algorithmic bytes per element.
+struct CloseList {
+  const double* p[kMaxVec];
+  double cN[kMaxVec], cA[kMaxVec], cB[kMaxVec];
+};
+hipError_t close_launch(double* outA, double* outB, const CloseList& P, int np, int64_t n,
+                        double* partial, hipStream_t s, int64_t* nblk);
 // result[k] = sum_b partial[k*nblk + b] for k < nsum, NaN-propagating max for nsum <= k < nv.
 // result_host (optional): pinned host memory the kernel also writes (zero-copy readback).
 hipError_t reduce_final_launch(const double* partial, int64_t nblk, int nsum, int nv,

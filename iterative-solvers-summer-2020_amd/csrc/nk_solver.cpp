@@ -420,13 +420,17 @@ void givens(double a, double b, double* c, double* s) {
 // Least-squares solve of the (n x n) upper-triangular R y = g (lstsq in _gcrotmk.py:177):
 // back-substitution when R is well conditioned on its diagonal, otherwise a one-sided Jacobi
 // SVD pseudo-inverse with gelsd's cut-off rcond = eps * n.
-void lstsq_upper(const double (*R)[kMaxVec + 1], int n, const double* g, double* y) {
+bool lstsq_upper_direct(const double (*R)[kMaxVec + 1], int n) {
   double dmax = 0.0, dmin = INFINITY;
   for (int i = 0; i < n; ++i) {
     dmax = std::max(dmax, std::fabs(R[i][i]));
     dmin = std::min(dmin, std::fabs(R[i][i]));
   }
-  if (n > 0 && dmin > kEps * n * dmax) {
+  return n > 0 && dmin > kEps * n * dmax;
+}
+
+void lstsq_upper(const double (*R)[kMaxVec + 1], int n, const double* g, double* y) {
+  if (lstsq_upper_direct(R, n)) {
     for (int i = n - 1; i >= 0; --i) {
       double acc = g[i];
       for (int k = i + 1; k < n; ++k) acc -= R[i][k] * y[k];

@@ -360,6 +360,8 @@ nk_opts default_opts();
 namespace detail {
 void givens(double a, double b, double* c, double* s);
 void lstsq_upper(const double (*R)[kMaxVec + 1], int n, const double* g, double* y);
+// lstsq_upper solves this system by back substitution (not by its singular fallback)
+bool lstsq_upper_direct(const double (*R)[kMaxVec + 1], int n);
 }  // namespace detail
 
 }  // namespace nk

@@ -206,6 +206,32 @@ def maxpy(V, coef, y):
     return y
 
 
+def lgmres_close(P, cN, cA, cB, A=None, B=None):
+    """The closing pass of an LGMRES cycle (csrc/krylov.hip close_launch) on caller tensors: one
+    read of the distinct vectors ``P`` gives ``A = sum cA[i] P[i]``, ``B = sum cB[i] P[i]`` and
+    ``sum((sum cN[i] P[i])**2)``, each sum in list order.  Returns ``(A, B, norm2)``.  The
+    kernel's contract is distinct inputs: a tensor listed twice is rejected."""
+    m = len(P)
+    if m < 1 or not (len(cN) == len(cA) == len(cB) == m):
+        raise ValueError("lgmres_close: one (cN, cA, cB) triple per vector, at least one vector")
+    for i, p in enumerate(P):
+        _dev(p, "P[i]")
+        if p.numel() != P[0].numel():
+            raise ValueError("lgmres_close: size mismatch")
+    if len({p.data_ptr() for p in P}) != m:
+        raise ValueError("lgmres_close: the vectors must be distinct (one list entry per tensor)")
+    A = torch.empty_like(P[0]) if A is None else _dev(A, "A")
+    B = torch.empty_like(P[0]) if B is None else _dev(B, "B")
+    if A.numel() != P[0].numel() or B.numel() != P[0].numel():
+        raise ValueError("lgmres_close: size mismatch")
+    ptrs = (C.c_void_p * m)(*[p.data_ptr() for p in P])
+    arr = [(C.c_double * m)(*[float(c) for c in cs]) for cs in (cN, cA, cB)]
+    r = C.c_double()
+    check(lib.nk_debug_close(ptrs, *arr, m, P[0].numel(), _ptr(A), _ptr(B), C.byref(r),
+                             _stream()), "nk_debug_close")
+    return A, B, r.value
+
+
 def stream_copy(src, out=None):
     """out = src through nk_stream_copy (16-KB chunks per block, non-temporal): the bench's probe
     of the box's achievable streaming rate."""
