@@ -214,6 +214,48 @@ int nk_debug_ctl_step(int32_t form, int32_t t, const int32_t* ints, const double
                       const double* sig, const double* h, const double* cs, const double* sn,
                       const double* gram, const double* red, void* state_out, void* mirror_out,
                       double* prm_out, uint32_t* status_out);
+/* One stencil pass on caller tensors, through the solver's own launch: any
+ * of the eight pass modes, on a whole periodic grid or on a row slab with halo rows, whole or as
+ * a row range, with every optional input and output the solver's passes use.  All pointers are
+ * device pointers; NULL = not used.  Every field is 8 bytes wide. */
+typedef struct nk_stencil_pass {
+  int64_t mode;          /* 0 LAP5, 1 SH13, 2 RESID, 3 BOLD, 4 TRIAL, 5 FDJVP, 6 AJVP, 7 LINOP */
+  int64_t ny, nx;        /* the slab */
+  int64_t r0, r1;        /* rows [r0, r1) are computed, as SHProblem's interior / edge launches
+                          * (ny >= 4); r1 < 0: the whole slab */
+  const double* a;       /* the stencil field (RESID: u; BOLD: uo; AJVP: z; else x of x + alpha b) */
+  const double* a_halo;  /* 4 rows of nx: the slab's rows -2, -1, ny, ny+1; NULL: periodic */
+  const double* b;       /* second field (RESID: uo; TRIAL / FDJVP / LINOP: b of a + alpha b) */
+  const double* b_halo;
+  const double* p0;      /* point-wise input (TRIAL: B; FDJVP: G0; AJVP: u; LINOP: D) */
+  double* out0;
+  double* out1;          /* TRIAL: G */
+  double* out2;          /* TRIAL (optional), LINOP: a + alpha b */
+  double alpha, sc, e, theta;
+  double h, r, k, g;     /* the 13-point coefficients, the time step and the quadratic term */
+  const double* znorm2;  /* FDJVP / AJVP: the scales come from this device value and omega */
+  double omega;
+  const double* spec;    /* FDJVP: 3 doubles (sum F^2, max|F|, max|x|); the speculative gate */
+  double spec_thr, spec_ftol, spec_rdiff, spec_zn, spec_zs;
+  const double* Ea;      /* edge arrays (nk_edge_elems(ny, nx) values) of a and b: side columns */
+  const double* Eb;
+  double* E0;            /* edge arrays of out0 / out2, written by the pass */
+  double* E2;
+  /* pushed halo rows: out0's rows 0, 1 go into rows 2, 3 of slot PS0[0] and its rows ny-2, ny-1
+   * into rows 0, 1 of slot PS0[1] (4 rows of ps_ld >= nx each; both or neither; ny >= 4); PS2:
+   * the same for out2 (TRIAL) */
+  double* PS0[2];
+  double* PS2[2];
+  int64_t ps_ld;
+  int64_t rev;           /* band walk: -1 alternates per call as in the solver, 0 / 1 forces it
+                          * from the bottom / top */
+} nk_stencil_pass;
+/* Runs the pass and synchronises `stream`.  TRIAL: red[0..2] = sum out0^2, max|out0|,
+ * max|out2|; LINOP: red[0] = sum out2 out0 (reduced from the pass's per-block partials as the
+ * solver reduces them); *nblk = the pass's block count.  NK_EINVAL for arguments the mode
+ * needs and does not have, NK_EHIP when the launch refuses them (edge arrays or halo slots
+ * with a grid only the point kernel takes).  Diagnostic only: no reference interface. */
+int nk_debug_stencil(const nk_stencil_pass* p, double* red, int64_t* nblk, void* stream);
 
 /* ---------------- communicators (row-slab decomposition over RCCL / xGMI) ---------------- */
 int nk_comm_unique_id_bytes(void);

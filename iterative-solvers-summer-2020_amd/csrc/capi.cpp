@@ -459,6 +459,106 @@ int nk_debug_ctl_step(int32_t form, int32_t t, const int32_t* ints, const double
   return hip_rc(e);
 }
 
+// One stencil pass on caller tensors: the arguments go into a StencilArgs as SHProblem fills its
+// own (field(), stencil_rows(), the edge / push fields) and through stencil_launch; the reducing
+// modes' partials are reduced as Engine::reduce does (reduce_final_launch).
+int nk_debug_stencil(const nk_stencil_pass* p, double* red, int64_t* nblk_out, void* stream) {
+  if (!p || p->mode < 0 || p->mode > 7 || p->ny <= 0 || p->nx <= 0 || !p->a || !p->out0)
+    return NK_EINVAL;
+  const SMode m = static_cast<SMode>(int(p->mode));
+  const bool two = m == SMode::RESID || m == SMode::TRIAL || m == SMode::FDJVP || m == SMode::LINOP;
+  const bool has_p0 = m == SMode::TRIAL || m == SMode::FDJVP || m == SMode::AJVP || m == SMode::LINOP;
+  const bool reduces = m == SMode::TRIAL || m == SMode::LINOP;
+  if ((two && !p->b) || (has_p0 && !p->p0) || (m == SMode::TRIAL && !p->out1) ||
+      (m == SMode::LINOP && !p->out2) || (reduces && !red))
+    return NK_EINVAL;
+  if (m == SMode::FDJVP && !p->znorm2 && !p->spec && !(p->sc != 0.0)) return NK_EINVAL;
+  const bool ranged = p->r1 >= 0;
+  if (ranged && (p->ny < 4 || p->r0 < 0 || p->r0 >= p->r1 || p->r1 > p->ny || p->r0 == 1 ||
+                 p->r1 == p->ny - 1))
+    return NK_EINVAL;  // stencil_rows: the range's halo rows lie inside the slab or in its halo
+  const bool push0 = p->PS0[0] || p->PS0[1], push2 = p->PS2[0] || p->PS2[1];
+  if ((push0 && (!p->PS0[0] || !p->PS0[1])) || (push2 && (!p->PS2[0] || !p->PS2[1])) ||
+      (push2 && !(m == SMode::TRIAL && p->out2)) ||
+      ((push0 || push2) && (p->ny < 4 || p->ps_ld < p->nx || p->ps_ld % 2)))
+    return NK_EINVAL;
+  for (const void* q : {(const void*)p->Ea, (const void*)p->Eb, (const void*)p->E0,
+                        (const void*)p->E2, (const void*)p->PS0[0], (const void*)p->PS0[1],
+                        (const void*)p->PS2[0], (const void*)p->PS2[1]})
+    if (reinterpret_cast<uintptr_t>(q) & 15u) return NK_EINVAL;
+  if (p->E2 && m != SMode::TRIAL) return NK_EINVAL;
+  if (p->rev < -1 || p->rev > 1) return NK_EINVAL;
+
+  StencilArgs A;
+  A.ny = p->ny;
+  A.nx = p->nx;
+  auto field = [&](const double* base, const double* halo) {
+    return halo ? Field{base, halo, halo + 2 * p->nx} : periodic(base);  // SHProblem::field
+  };
+  A.a = field(p->a, p->a_halo);
+  if (p->b) A.b = (p->b == p->a && p->b_halo == p->a_halo) ? A.a : field(p->b, p->b_halo);
+  A.alpha = p->alpha;
+  A.p0 = p->p0;
+  A.out0 = p->out0;
+  A.out1 = p->out1;
+  A.out2 = p->out2;
+  A.e = p->e;
+  A.c = sh_coef(p->h, p->r, p->k, p->g);
+  A.sc = p->sc;
+  A.znorm2 = p->znorm2;
+  A.omega = p->omega;
+  A.spec = p->spec;
+  A.spec_thr = p->spec_thr;
+  A.spec_ftol = p->spec_ftol;
+  A.spec_rdiff = p->spec_rdiff;
+  A.spec_zn = p->spec_zn;
+  A.spec_zs = p->spec_zs;
+  A.theta = p->theta;
+  A.Ea = p->Ea;
+  A.Eb = p->Eb;
+  A.E0 = p->E0;
+  A.E2 = p->E2;
+  A.e_ny = p->ny;
+  A.e_row0 = 0;
+  for (int i = 0; i < 2; ++i) {
+    A.PS0[i] = p->PS0[i];
+    A.PS2[i] = p->PS2[i];
+  }
+  A.ps_ld = p->ps_ld;
+  A.rev_force = int(p->rev);
+  const StencilArgs L = ranged ? stencil_rows(A, p->r0, p->r1) : A;
+
+  hipStream_t s = S(stream);
+  double* buf = nullptr;
+  const int64_t slots = stencil_partial_slots(p->ny, p->nx);
+  hipError_t e = hipSuccess;
+  StencilArgs R = L;
+  if (reduces) {
+    // an unwritten partial slot must not pass for a sum: all-ones bytes are NaNs
+    e = hipMallocAsync(reinterpret_cast<void**>(&buf), sizeof(double) * (slots + 3), s);
+    if (e == hipSuccess) e = hipMemsetAsync(buf, 0xff, sizeof(double) * (slots + 3), s);
+    if (e != hipSuccess) {
+      if (buf) hipFreeAsync(buf, s);
+      return hip_rc(e);
+    }
+    R.partial = buf;
+  }
+  int64_t nblk = 0;
+  e = stencil_launch(m, R, s, &nblk);
+  double host[3] = {0.0, 0.0, 0.0};
+  const int nv = m == SMode::TRIAL ? 3 : 1;
+  if (reduces && e == hipSuccess && 3 * nblk > slots) e = hipErrorInvalidValue;
+  if (reduces && e == hipSuccess) e = reduce_final_launch(buf, nblk, 1, nv, buf + slots, nullptr, s);
+  if (reduces && e == hipSuccess)
+    e = hipMemcpyAsync(host, buf + slots, sizeof(double) * nv, hipMemcpyDeviceToHost, s);
+  if (buf) hipFreeAsync(buf, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hip_rc(e);
+  for (int i = 0; reduces && i < nv; ++i) red[i] = host[i];
+  if (nblk_out) *nblk_out = nblk;
+  return NK_OK;
+}
+
 // ------------------------------------------------------------------------------ comms
 int nk_comm_unique_id_bytes(void) { return comm_unique_id_bytes(); }
 int nk_comm_get_unique_id(void* out) { return out ? comm_get_unique_id(out) : NK_EINVAL; }

@@ -98,7 +98,9 @@ struct StencilArgs {
   double* PS0[2] = {};
   double* PS2[2] = {};
   int64_t ps_ld = 0;
-  bool rev = false;    // set by stencil_launch (traversal_reverse)
+  bool rev = false;    // set by stencil_launch (traversal_reverse, or rev_force)
+  int rev_force = -1;  // 0 / 1: stencil_launch walks the bands from the bottom / top instead of
+                       // asking traversal_reverse (tests: the walk must not depend on call history)
   bool nt_p0 = false;  // set by stencil_launch: non-temporal loads of the point-wise input
 };
 
@@ -108,6 +110,13 @@ struct StencilArgs {
 // NKHIP_PINGPONG=0 keeps every kernel forward.
 bool traversal_reverse();
 
+// Rows [r0, r1) of the slab pass A as a pass of its own (A.ny >= 2; r0 == 0 or r0 >= 2, r1 ==
+// A.ny or r1 <= A.ny - 2: both halo rows of a side come from one place): the two rows above /
+// below the range come from the slab itself or, at its top / bottom edge, from
+// the fields' halo rows (the slab's own last / first rows when it wraps periodically); the
+// point-wise input and the outputs start at row r0, the edge arrays keep their geometry
+// (e_row0 += r0).  SHProblem::halo_stencil overlaps the interior rows with the halo exchange so.
+StencilArgs stencil_rows(const StencilArgs& A, int64_t r0, int64_t r1);
 // Launches one stencil pass.  *nblk receives the number of partial-sum slots written (TRIAL).
 hipError_t stencil_launch(SMode m, const StencilArgs& a, hipStream_t s, int64_t* nblk);
 // Upper bound of the partial-sum slots one stencil pass with reductions (TRIAL) writes.

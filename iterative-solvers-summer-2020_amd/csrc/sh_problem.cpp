@@ -98,17 +98,18 @@ SHProblem::~SHProblem() {
 
 namespace {
 // Rows [r0, r1) of a slab field as a field of its own: the two rows above / below come from the
-// slab itself, or from the slab's halo at its top / bottom edge.
+// slab itself, or from the slab's halo at its top / bottom edge (a periodic slab: its own rows).
 Field sub_field(const Field& f, int64_t r0, int64_t r1, int64_t ny, int64_t nx) {
   if (!f.base) return f;
   Field s;
   s.base = f.base + r0 * nx;
-  s.lo = (r0 >= 2) ? f.base + (r0 - 2) * nx : f.lo;
-  s.hi = (r1 + 2 <= ny) ? f.base + r1 * nx : f.hi;
+  s.lo = (r0 >= 2) ? f.base + (r0 - 2) * nx : (f.lo ? f.lo : f.base + (ny - 2) * nx);
+  s.hi = (r1 + 2 <= ny) ? f.base + r1 * nx : (f.lo ? f.hi : f.base);
   return s;
 }
+}  // namespace
 
-StencilArgs sub_args(const StencilArgs& A, int64_t r0, int64_t r1) {
+StencilArgs stencil_rows(const StencilArgs& A, int64_t r0, int64_t r1) {
   StencilArgs B = A;
   B.ny = r1 - r0;
   B.a = sub_field(A.a, r0, r1, A.ny, A.nx);
@@ -121,7 +122,6 @@ StencilArgs sub_args(const StencilArgs& A, int64_t r0, int64_t r1) {
   if (A.out2) B.out2 = A.out2 + off;
   return B;
 }
-}  // namespace
 
 int SHProblem::halo_stencil(int kind, SMode m, const StencilArgs& A, const double* z, double* zh) {
   const double bytes = stencil_bytes_per_point(m, false);
@@ -137,12 +137,12 @@ int SHProblem::halo_stencil(int kind, SMode m, const StencilArgs& A, const doubl
   if (hipEventRecord(ev_in_, E_.s) != hipSuccess ||
       hipStreamWaitEvent(side_, ev_in_, 0) != hipSuccess)
     return NK_EHIP;
-  const StencilArgs I = sub_args(A, 2, ny_ - 2);
+  const StencilArgs I = stencil_rows(A, 2, ny_ - 2);
   if (stencil_launch(m, I, side_, nullptr) != hipSuccess) return NK_EHIP;
   if (hipEventRecord(ev_out_, side_) != hipSuccess) return NK_EHIP;
   int rc = halo(z, zh);
   if (rc) return rc;
-  const StencilArgs T = sub_args(A, 0, 2), Bm = sub_args(A, ny_ - 2, ny_);
+  const StencilArgs T = stencil_rows(A, 0, 2), Bm = stencil_rows(A, ny_ - 2, ny_);
   // the profile books the whole pass under `kind` (edges timed on the main stream, the interior
   // overlapping the exchange)
   rc = E_.launch(kind, bytes * ny_ * nx_, [&] {

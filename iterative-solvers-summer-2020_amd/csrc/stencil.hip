@@ -558,7 +558,7 @@ hipError_t launch_mode(const StencilArgs& A, hipStream_t s, int64_t* nblk) {
     const int64_t gy = (A.ny + RY - 1) / RY;
     if (gx * gy > (int64_t(1) << 31) - 8) return hipErrorInvalidValue;
     if (nblk) *nblk = gx * gy;
-    B.rev = traversal_reverse();
+    B.rev = (A.rev_force >= 0) ? A.rev_force != 0 : traversal_reverse();
     static const bool nt_p0 = env_int("NKHIP_NT_P0", 1) != 0;
     B.nt_p0 = nt_p0;
     const dim3 grid{unsigned((gx * gy + 7) / 8 * 8), 1u, 1u};

@@ -70,6 +70,20 @@ class nk_mems_params(C.Structure):
                 ("endl", C.c_double), ("endr", C.c_double), ("k", C.c_double)]
 
 
+class nk_stencil_pass(C.Structure):
+    """Arguments of nk_debug_stencil (include/nkhip.h): every field 8 bytes wide."""
+    _fields_ = ([(n, C.c_int64) for n in ("mode", "ny", "nx", "r0", "r1")]
+                + [(n, C.c_void_p) for n in ("a", "a_halo", "b", "b_halo", "p0", "out0", "out1",
+                                             "out2")]
+                + [(n, C.c_double) for n in ("alpha", "sc", "e", "theta", "h", "r", "k", "g")]
+                + [("znorm2", C.c_void_p), ("omega", C.c_double), ("spec", C.c_void_p)]
+                + [(n, C.c_double) for n in ("spec_thr", "spec_ftol", "spec_rdiff", "spec_zn",
+                                             "spec_zs")]
+                + [(n, C.c_void_p) for n in ("Ea", "Eb", "E0", "E2")]
+                + [("PS0", C.c_void_p * 2), ("PS2", C.c_void_p * 2), ("ps_ld", C.c_int64),
+                   ("rev", C.c_int64)])
+
+
 RESIDUAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 
 _P = C.c_void_p
@@ -110,6 +124,8 @@ SIGNATURES = [
     ("nk_debug_close", C.c_int, [C.POINTER(_P), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _I32,
                                  _I64, _P, _P, C.POINTER(_D), _P]),
     ("nk_debug_ctl_step", C.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("nk_debug_stencil", C.c_int, [C.POINTER(nk_stencil_pass), C.POINTER(_D), C.POINTER(_I64),
+                                   _P]),
     ("nk_comm_unique_id_bytes", C.c_int, []),
     ("nk_comm_get_unique_id", C.c_int, [_P]),
     ("nk_comm_create_rccl", C.c_int, [C.POINTER(_P), _P, _I32, _I32]),

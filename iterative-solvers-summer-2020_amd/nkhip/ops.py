@@ -232,6 +232,70 @@ def lgmres_close(P, cN, cA, cB, A=None, B=None):
     return A, B, r.value
 
 
+STENCIL_MODES = ("LAP5", "SH13", "RESID", "BOLD", "TRIAL", "FDJVP", "AJVP", "LINOP")
+
+
+def stencil_pass(mode, ny, nx, a, out0, *, b=None, p0=None, out1=None, out2=None, a_halo=None,
+                 b_halo=None, rows=None, alpha=0.0, sc=1.0, e=0.0, theta=0.0, h=1.0, r=0.0, k=1.0,
+                 g=0.0, znorm2=None, omega=0.0, spec=None, spec_thr=0.0, spec_ftol=0.0,
+                 spec_rdiff=0.0, spec_zn=1.0, spec_zs=1.0, Ea=None, Eb=None, E0=None, E2=None,
+                 PS0=None, PS2=None, ps_ld=0, rev=-1):
+    """One stencil pass (csrc/stencil.hip) of the solver on caller tensors, through
+    nk_debug_stencil: ``mode`` is a name of ``STENCIL_MODES`` or its number; ``a`` / ``b`` are
+    the (ny, nx) slab's fields with optional halos (4 rows of nx: rows -2, -1, ny, ny+1; None:
+    periodic), ``rows = (r0, r1)`` a row range, ``znorm2`` / ``spec`` device tensors of 1 / 3
+    values, ``Ea`` .. ``E2`` edge arrays, ``PS0`` / ``PS2`` pairs of halo-slot tensors with row
+    stride ``ps_ld``, ``rev`` the band walk (-1: as the solver alternates it).  Tensors are taken
+    as they are (views at any offset included): only their sizes are checked.  Returns
+    ``(red, nblk)``: the pass's reductions (TRIAL: [sum F^2, max|F|, max|w|]; LINOP: [w . out0];
+    else []) and its block count.  Diagnostic: the tests' way to every form of the pass."""
+    from ._lib import nk_stencil_pass
+
+    m = STENCIL_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    ny, nx = int(ny), int(nx)
+    P = nk_stencil_pass()
+    P.mode, P.ny, P.nx = m, ny, nx
+    P.r0, P.r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+
+    def dev(t, name, n):
+        if t is None:
+            return None
+        _dev(t, name)
+        if t.numel() < n:
+            raise ValueError(f"stencil_pass: {name} holds {t.numel()} values, needs {n}")
+        return t.data_ptr()
+
+    n = ny * nx
+    for name, t in (("a", a), ("b", b), ("p0", p0), ("out0", out0), ("out1", out1),
+                    ("out2", out2)):
+        setattr(P, name, dev(t, name, n))
+    P.a_halo = dev(a_halo, "a_halo", 4 * nx)
+    P.b_halo = dev(b_halo, "b_halo", 4 * nx)
+    P.alpha, P.sc, P.e, P.theta = float(alpha), float(sc), float(e), float(theta)
+    P.h, P.r, P.k, P.g = float(h), float(r), float(k), float(g)
+    P.znorm2, P.omega = dev(znorm2, "znorm2", 1), float(omega)
+    P.spec = dev(spec, "spec", 3)
+    P.spec_thr, P.spec_ftol, P.spec_rdiff = float(spec_thr), float(spec_ftol), float(spec_rdiff)
+    P.spec_zn, P.spec_zs = float(spec_zn), float(spec_zs)
+    ne = int(lib.nk_edge_elems(ny, nx))
+    for name, t in (("Ea", Ea), ("Eb", Eb), ("E0", E0), ("E2", E2)):
+        setattr(P, name, dev(t, name, ne))
+    P.ps_ld = int(ps_ld)
+    for name, pair in (("PS0", PS0), ("PS2", PS2)):
+        if pair is not None:
+            if len(pair) != 2 or P.ps_ld < nx:
+                raise ValueError(f"stencil_pass: {name} is a (prev, next) pair of slots, ps_ld >= nx")
+            arr = getattr(P, name)
+            for i, t in enumerate(pair):
+                arr[i] = dev(t, name, 4 * P.ps_ld)
+    P.rev = int(rev)
+    red = (C.c_double * 3)()
+    nblk = C.c_int64(0)
+    check(lib.nk_debug_stencil(C.byref(P), red, C.byref(nblk), _stream()), "nk_debug_stencil")
+    nred = {4: 3, 7: 1}.get(m, 0)
+    return [red[i] for i in range(nred)], nblk.value
+
+
 def stream_copy(src, out=None):
     """out = src through nk_stream_copy (16-KB chunks per block, non-temporal): the bench's probe
     of the box's achievable streaming rate."""
