@@ -353,8 +353,14 @@ typedef struct nk_drop_params {
 typedef struct nk_drop nk_drop;
 
 int nk_drop_params_default(nk_drop_params* p);
+/* nx, ny >= 7 (a 3-wide boundary ring and at least one interior point per side), else NK_EINVAL */
 int nk_drop_create(nk_drop** out, const nk_drop_params* p, const nk_opts* opts, void* stream);
 int nk_drop_destroy(nk_drop* d);
+/* Which kernels an nx x ny grid (droplet or MEMS, n x n) runs on: 1 = the LDS-resident residual
+ * and PMA kernels (three planes of ny * (nx|1) doubles fit the dynamic LDS cap), 0 = the ones
+ * that keep every field in global memory (also forced at any size by NKHIP_DROP_GLOBAL=1).
+ * Host only.  NK_EINVAL for a side below 7. */
+int nk_drop_lds_fits(int32_t nx, int32_t ny);
 /* state: U.new (= U.val) and the mesh potential Q.val, device arrays of nx*ny */
 int nk_drop_set_state(nk_drop* d, const double* U_dev, const double* Q_dev);
 int nk_drop_get_state(nk_drop* d, double* U_dev, double* Q_dev);

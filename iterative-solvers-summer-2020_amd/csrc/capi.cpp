@@ -891,6 +891,11 @@ int nk_drop_create(nk_drop** out, const nk_drop_params* p, const nk_opts* opts, 
   return NK_OK;
 }
 
+int nk_drop_lds_fits(int32_t nx, int32_t ny) {
+  if (nx < 7 || ny < 7) return NK_EINVAL;
+  return drop_lds_fits(nx, ny) ? 1 : 0;
+}
+
 static DropletStepper* DS(nk_drop* d) { return reinterpret_cast<DropletStepper*>(d); }
 
 int nk_drop_destroy(nk_drop* d) {

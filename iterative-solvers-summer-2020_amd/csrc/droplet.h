@@ -40,6 +40,11 @@ struct DropScratch {
   double *w, *ud, *ue, *t1, *t2, *p, *A, *B;
 };
 
+// Which variant the residual and PMA launchers below take for an nx x ny grid: the LDS-resident
+// kernels when their three working planes fit the dynamic LDS cap (true), else the ones that keep
+// every field in global scratch.  (NKHIP_DROP_GLOBAL=1 forces the latter at any size.)
+bool drop_lds_fits(int nx, int ny);
+
 // Q -> DropMesh (one single-workgroup launch).
 hipError_t drop_mesh_launch(const DropParams& P, const double* q, DropMesh M, hipStream_t s);
 

@@ -193,11 +193,12 @@ __device__ __forceinline__ double pressure(const DropParams& P, double h, double
 // boundary ring with the general per-position code.  Only the one wave straddling the split
 // diverges; a row-major walk would put boundary columns in nearly every wave.
 // Division by a run-time divisor d as one multiply-high: q = umulhi(t, ceil(2^32/d)), exact
-// while t*d < 2^32 (shape_ok bounds the grid so).
+// while t*d < 2^32 (shape_ok bounds the grid so).  d == 1 (the interior of a 7-wide grid) has no
+// 32-bit multiplier -- ceil(2^32/1) wraps to 0 -- so m == 0 stands for "the quotient is t".
 struct FastDiv {
   uint32_t m;
   __device__ explicit FastDiv(uint32_t d) : m(0xFFFFFFFFu / d + 1u) {}
-  __device__ int operator()(int t) const { return int(__umulhi(uint32_t(t), m)); }
+  __device__ int operator()(int t) const { return m ? int(__umulhi(uint32_t(t), m)) : t; }
 };
 
 // point u of the boundary ring: rows 0-2 and ny-3..ny-1, then columns 0-2 and nx-3..nx-1 of
@@ -1074,13 +1075,19 @@ Coefs make_coefs(const DropParams& P) {
   return C;
 }
 
-// >= 7 points per side (3-wide boundary ring + interior); FastDiv exact: NN * max(nx, ny) < 2^32
+// >= 7 points per side (3-wide boundary ring + an interior of at least one point, the divisor
+// FastDiv takes as it is); FastDiv exact: NN * max(nx, ny) < 2^32
 bool shape_ok(const DropParams& P) {
   return P.nx >= 7 && P.ny >= 7 &&
          double(P.nx) * P.ny * (P.nx > P.ny ? P.nx : P.ny) < 4294967295.0;
 }
 
+// the three working planes of the LDS-resident kernels (row stride nx|1)
+size_t lds_bytes(int nx, int ny) { return 3 * size_t(ny) * (nx | 1) * sizeof(double); }
+
 }  // namespace
+
+bool drop_lds_fits(int nx, int ny) { return lds_bytes(nx, ny) <= kPmaLdsMax; }
 
 hipError_t drop_mesh_launch(const DropParams& P, const double* q, DropMesh M, hipStream_t s) {
   if (!shape_ok(P)) return hipErrorInvalidValue;
@@ -1102,9 +1109,9 @@ hipError_t drop_resid_launch(const DropParams& P, DropMesh M, DropScratch S, con
                              double* xt, double* partial, hipStream_t s, const double* znorm2,
                              double omega, const double* prm) {
   if (!shape_ok(P)) return hipErrorInvalidValue;
-  const size_t lds = 3 * size_t(P.ny) * (P.nx | 1) * sizeof(double);
+  const size_t lds = lds_bytes(P.nx, P.ny);
   const bool force_global = env_flag("NKHIP_DROP_GLOBAL") != 0;  // (read per launch: tests flip it)
-  if (!force_global && lds <= kPmaLdsMax) {
+  if (!force_global && drop_lds_fits(P.nx, P.ny)) {
     static const hipError_t attr = hipFuncSetAttribute(
         reinterpret_cast<const void*>(&drop_resid_kernel<true>),
         hipFuncAttributeMaxDynamicSharedMemorySize, int(kPmaLdsMax));
@@ -1132,9 +1139,9 @@ hipError_t mems_resid_launch(const DropParams& P, const MemsParams& Mp, DropMesh
                              double* xt, double* uxx, double* uyy, double* partial, hipStream_t s,
                              const double* znorm2, double omega, const double* prm) {
   if (!shape_ok(P) || mode < 0 || mode > 2) return hipErrorInvalidValue;
-  const size_t lds = 3 * size_t(P.ny) * (P.nx | 1) * sizeof(double);
+  const size_t lds = lds_bytes(P.nx, P.ny);
   const bool force_global = env_flag("NKHIP_DROP_GLOBAL") != 0;  // (read per launch: tests flip it)
-  if (!force_global && lds <= kPmaLdsMax) {
+  if (!force_global && drop_lds_fits(P.nx, P.ny)) {
     static const hipError_t attr = hipFuncSetAttribute(
         reinterpret_cast<const void*>(&mems_resid_kernel<true>),
         hipFuncAttributeMaxDynamicSharedMemorySize, int(kPmaLdsMax));
@@ -1259,9 +1266,9 @@ hipError_t drop_pma_launch(const DropParams& P, DropMesh M, DropScratch S, doubl
     if (env_flag("NKHIP_PMA_TIMING") && hipMalloc(&t, 64) != hipSuccess) t = nullptr;
     return t;
   }();
-  const size_t lds = 3 * size_t(P.ny) * (P.nx | 1) * sizeof(double);
+  const size_t lds = lds_bytes(P.nx, P.ny);
   const bool force_global = env_flag("NKHIP_DROP_GLOBAL") != 0;  // (read per launch: tests flip it)
-  if (!force_global && lds <= kPmaLdsMax) {
+  if (!force_global && drop_lds_fits(P.nx, P.ny)) {
     static const hipError_t attr = hipFuncSetAttribute(
         reinterpret_cast<const void*>(&drop_pma_lds_kernel),
         hipFuncAttributeMaxDynamicSharedMemorySize, int(kPmaLdsMax));

@@ -153,6 +153,7 @@ SIGNATURES = [
     ("nk_drop_create", C.c_int, [C.POINTER(_P), C.POINTER(nk_drop_params), C.POINTER(nk_opts),
                                  _P]),
     ("nk_drop_destroy", C.c_int, [_P]),
+    ("nk_drop_lds_fits", C.c_int, [_I32, _I32]),
     ("nk_drop_set_state", C.c_int, [_P, _P, _P]),
     ("nk_drop_get_state", C.c_int, [_P, _P, _P]),
     ("nk_drop_step", C.c_int, [_P, _D, _D, _I32, C.POINTER(nk_stats), C.POINTER(_D),

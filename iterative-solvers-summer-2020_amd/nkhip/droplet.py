@@ -52,6 +52,12 @@ def write_init(path, U, Q):
             fh.write(str(u) + " " + str(q) + "\n")
 
 
+def lds_fits(nx, ny):
+    """Whether an nx x ny grid runs on the LDS-resident residual / PMA kernels (True) or on the
+    ones that keep every field in global memory (nk_drop_lds_fits; host only)."""
+    return bool(check(lib.nk_drop_lds_fits(int(nx), int(ny)), "nk_drop_lds_fits"))
+
+
 class Droplet:
     """The droplet.py stepper; keyword arguments override the module globals (:22-53)."""
 
@@ -168,9 +174,15 @@ class Droplet:
         check(lib.nk_drop_field(self._h, FIELDS[name], C.c_void_p(out.data_ptr())), "nk_drop_field")
         return out
 
-    def residual(self, u, dt):
+    def residual(self, u, dt, out=None):
+        """residual(u, F, dt) (:435-450).  `out`: a contiguous fp64 device tensor of nx*ny values
+        to write into (a test prefills it, so a point the kernel skips shows)."""
         u = self._dev(u)
-        out = torch.empty_like(u)
+        if out is None:
+            out = torch.empty_like(u)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64
+                  and out.is_contiguous() and out.numel() == self.n):
+            raise ValueError(f"out must be a contiguous float64 device tensor of {self.n} values")
         check(lib.nk_drop_residual(self._h, C.c_void_p(u.data_ptr()), float(dt),
                                    C.c_void_p(out.data_ptr())), "nk_drop_residual")
         return out

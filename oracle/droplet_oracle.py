@@ -8,6 +8,9 @@ Layout: u[i*Nx + j], i = eta (row, Ny = 61), j = xi (column, Nx = 91) -- ``ksiks
 ``np.meshgrid`` (droplet.py:60), so x varies fastest.  Boundary index sets (make_Ibdy :762-776):
 Left = column 0, Right = column Nx-1, Bottom = row 0, Top = row Ny-1.
 
+``configure(nx, ny, dtype)`` rebuilds the grid-dependent globals for another grid or for extended
+precision (the module starts at 91 x 61 in fp64); ``deformed_state`` is the other-grid tests' input.
+
 Every function cites the reference lines it restates.  Reference quirks kept on purpose (SURVEY
 8a row D2): compute_u_spatial_ders zeroes U_dksi[Bottom] where U_deta was probably meant (:722);
 M.Leig is divided by dksi*deta (:833); A11/A22/A12 are recomputed from Q on every Laplace call
@@ -28,23 +31,18 @@ P = SimpleNamespace(
     alpha2=0.0, n=6, m=3, Bo=0.01,
 )  # a: droplet profile sharpness (:23)
 P.a = 100.0
-P.NN = P.Nx * P.Ny
 P.Dx = P.endr - P.endl
 P.Dy = P.endt - P.endb
-P.dksi = P.Dx / (P.Nx - 1)
-P.deta = P.Dy / (P.Ny - 1)
-P.dksi2 = P.dksi * P.dksi
-P.deta2 = P.deta * P.deta
 P.epsilon2 = 1.0 / P.Dy
 
 INIT_FILE = "initdrop_coal_1_91-61_100_0.01_0.01_0.1_0.15.txt"
 
 
 # ---------------------------------------------------------------- 1-D operators (make_M :778-833)
-def _d1_matrix(n, h):
+def _d1_matrix(n, h, dtype=np.float64):
     """dksiCentre / detaCentre 1-D factor (:795-806): 4th-order centred first derivative with
     one-sided closures on the two outer rows at each end."""
-    A = np.zeros((n, n))
+    A = np.zeros((n, n), dtype=dtype)
     for i in range(2, n - 2):
         A[i, i - 2:i + 3] = [1, -8, 0, 8, -1]
     A[0, :5] = [-25, 48, -36, 16, -3]
@@ -54,22 +52,55 @@ def _d1_matrix(n, h):
     return A / (12 * h)
 
 
-def _d2_matrix(n, h2):
-    """d2ksi / d2eta 1-D factor (:782-793)."""
-    A = np.zeros((n, n))
+def _d2_matrix(n, h2, dtype=np.float64):
+    """d2ksi / d2eta 1-D factor (:782-793).  The non-integer weights are formed in `dtype`, so an
+    extended-precision matrix does not inherit their fp64 rounding."""
+    A = np.zeros((n, n), dtype=dtype)
+    one = dtype(1)
     for i in range(2, n - 2):
         A[i, i - 2:i + 3] = [-1, 16, -30, 16, -1]
-    A[0, :5] = [-415 / 6, 96, -36, 32 / 3, -1.5]
+    A[0, :5] = [-415 * one / 6, 96, -36, 32 * one / 3, -1.5]
     A[1, :6] = [10, -15, -4, 14, -6, 1]
-    A[-1, -5:] = [-1.5, 32 / 3, -36, 96, -415 / 6]
+    A[-1, -5:] = [-1.5, 32 * one / 3, -36, 96, -415 * one / 6]
     A[-2, -6:] = [1, -6, 14, -4, -15, 10]
     return A / (12 * h2)
 
 
-D1X = _d1_matrix(P.Nx, P.dksi)
-D1Y = _d1_matrix(P.Ny, P.deta)
-D2X = _d2_matrix(P.Nx, P.dksi2)
-D2Y = _d2_matrix(P.Ny, P.deta2)
+def _idx():
+    I = np.arange(P.NN).reshape(P.Ny, P.Nx)
+    return SimpleNamespace(Left=I[:, 0], Right=I[:, -1], Bottom=I[0, :], Top=I[-1, :],
+                           Boundary=np.unique(np.concatenate([I[:, 0], I[:, -1], I[0, :], I[-1, :]])))
+
+
+def configure(nx, ny, dtype=np.float64):
+    """The grid-dependent globals for an nx x ny grid (the reference's 91 x 61; other sizes take
+    the GPU kernels through their other strip, tile and memory paths) in precision `dtype`.
+
+    With ``dtype=np.longdouble`` and longdouble inputs every function below computes in extended
+    precision: the reference that the fp64 kernels (and this module's own fp64 rounding) are
+    measured against.  That needs a longdouble wider than fp64 (x87: eps = 1.08e-19)."""
+    global D1X, D1Y, D2X, D2Y, IB
+    if dtype is not np.float64 and not np.finfo(dtype).eps < 1e-18:
+        raise ImportError(
+            f"oracle.droplet_oracle: {np.dtype(dtype).name} has eps = {np.finfo(dtype).eps:.3g} "
+            "here (>= 1e-18): no extended-precision reference on this platform")
+    # fp64: plain Python floats, exactly what the module has always held
+    num = float if dtype is np.float64 else dtype
+    P.dtype = dtype
+    P.Nx, P.Ny, P.NN = nx, ny, nx * ny
+    P.dksi = num(dtype(P.Dx) / (nx - 1))
+    P.deta = num(dtype(P.Dy) / (ny - 1))
+    P.dksi2 = P.dksi * P.dksi
+    P.deta2 = P.deta * P.deta
+    P.pi = np.pi if dtype is np.float64 else 4 * np.arctan(dtype(1))
+    D1X = _d1_matrix(nx, P.dksi, dtype)
+    D1Y = _d1_matrix(ny, P.deta, dtype)
+    D2X = _d2_matrix(nx, P.dksi2, dtype)
+    D2Y = _d2_matrix(ny, P.deta2, dtype)
+    IB = _idx()
+
+
+configure(P.Nx, P.Ny)
 
 
 def dksi(v):
@@ -95,19 +126,10 @@ def dksideta(v):
     return (D1Y @ v.reshape(P.Ny, P.Nx) @ D1X.T).reshape(-1)
 
 
-def _idx():
-    I = np.arange(P.NN).reshape(P.Ny, P.Nx)
-    return SimpleNamespace(Left=I[:, 0], Right=I[:, -1], Bottom=I[0, :], Top=I[-1, :],
-                           Boundary=np.unique(np.concatenate([I[:, 0], I[:, -1], I[0, :], I[-1, :]])))
-
-
-IB = _idx()
-
-
 def leig():
     """M.Leig (:829-833), including the division by dksi*deta."""
-    t = (2 * np.cos(np.pi * np.arange(P.Ny) / (P.Ny - 1)) - 2).reshape(P.Ny, 1) * np.ones(P.Nx) + \
-        np.ones((P.Ny, 1)) * (2 * np.cos(np.pi * np.arange(P.Nx) / (P.Nx - 1)) - 2)
+    t = (2 * np.cos(P.pi * np.arange(P.Ny) / (P.Ny - 1)) - 2).reshape(P.Ny, 1) * np.ones(P.Nx) + \
+        np.ones((P.Ny, 1)) * (2 * np.cos(P.pi * np.arange(P.Nx) / (P.Nx - 1)) - 2)
     return t / (P.dksi * P.deta)
 
 
@@ -150,8 +172,8 @@ def laplace(v, v_dksi, v_deta, Q):
     A11 = A11f.reshape(P.Ny, P.Nx)
     A22 = A22f.reshape(P.Ny, P.Nx)
     v = v.reshape(P.Ny, P.Nx)
-    vxx = np.zeros((P.Ny, P.Nx))
-    vyy = np.zeros((P.Ny, P.Nx))
+    vxx = np.zeros((P.Ny, P.Nx), dtype=v.dtype)
+    vyy = np.zeros((P.Ny, P.Nx), dtype=v.dtype)
     dx2, dy2 = P.dksi2, P.deta2
     vxx[:, 3:-3] = (4 * A11[:, 2:-4] * (v[:, :-6] - 8 * v[:, 1:-5] + 8 * v[:, 3:-3] - v[:, 4:-2])
                     - (-A11[:, 1:-5] + 9 * A11[:, 2:-4] + 9 * A11[:, 3:-3] - A11[:, 4:-2])
@@ -265,7 +287,7 @@ def monitor(U, Q):
     """compute_and_smooth_monitor (:729-760)."""
     temp = (np.abs(U.xx + U.yy) ** 2).reshape(P.Ny, P.Nx)
     Nx, Ny = P.Nx, P.Ny
-    mon = np.zeros((Ny, Nx))
+    mon = np.zeros((Ny, Nx), dtype=temp.dtype)
     for _ in range(P.smoothing_iters):
         mon[1:-1, 1:-1] = temp[1:-1, 1:-1] + (temp[:-2, 1:-1] + temp[2:, 1:-1] + temp[1:-1, :-2] + temp[1:-1, 2:]) / 8 \
             + (temp[:-2, :-2] + temp[:-2, 2:] + temp[2:, :-2] + temp[2:, 2:]) / 16
@@ -341,7 +363,7 @@ def H2(psi, R, V):
 def compute_U2(info, Q):
     """compute_U2 (:413-423): precursor film plus one parabolic cap per (x, y, R, V) droplet,
     evaluated at the physical node coordinates (Q.dksi, Q.deta)."""
-    ret = np.full(P.NN, P.epsilon)
+    ret = np.full(P.NN, P.epsilon, dtype=P.dtype)
     for x, y, R, V in info:
         ret += (1 - P.epsilon) * H2(G2(np.sqrt((Q.dksi - x) ** 2 + (Q.deta - y) ** 2), R), R, V)
     return ret
@@ -368,3 +390,24 @@ def init_coalescing(vsteps=1000, info=((0, 0, 1, 1), (3, 0, 1, 1)), dtmesh=5e-9,
         unew = compute_U2(arg, Q)
         qval = loop_pma(qval, uval, dtmesh, loops, Q=Q, U=U)
     return unew, qval
+
+
+# ------------------------------------------------------------------ a mesh far from the identity
+def deformed_state(nx, ny):
+    """(U, Q, u1) in fp64 on an nx x ny grid: the input of the other-grid tests.
+
+    Every state the reference itself produces keeps the mesh close to the identity (min J ~ 0.9994
+    after the flat film's first loops), where dksideta, A12 and with them every cross term of the
+    Laplace operator, the flux and the pressure derivatives nearly vanish.  Here the potential of
+    the identity map carries two smooth modes, Q = Q0 + 0.25 cos(pi X) cos(pi Y) + 0.1 cos(2 pi X)
+    cos(3 pi Y) on the unit square (X, Y), which puts J in about [0.59, 1.46] and max|dksideta| at
+    0.12-0.14; U is two half-volume droplets on that mesh and u1 a 1e-3 relative perturbation of
+    it (a fixed seed per grid).  Leaves the module configured for (nx, ny) in fp64."""
+    configure(nx, ny)
+    _, q0 = initial_mesh()
+    X, Y = np.meshgrid(np.linspace(0, 1, nx), np.linspace(0, 1, ny))
+    q = q0 + (0.25 * np.cos(np.pi * X) * np.cos(np.pi * Y)
+              + 0.1 * np.cos(2 * np.pi * X) * np.cos(3 * np.pi * Y)).reshape(-1)
+    u = compute_U2([(0, 0, 1, 0.5), (3, 0, 1, 0.5)], q_ders(q))
+    u1 = u * (1 + 1e-3 * np.random.default_rng(1000 * nx + ny).standard_normal(P.NN))
+    return u, q, u1

@@ -53,12 +53,27 @@ def test_newton_krylov_fixed_mesh(drop):
     assert drop.last_stats["fnorm_inf"] <= 1e-7
 
 
+def _increment_5(Q):
+    """The error of Q after 5 PMA loops in its increment, relative to the reference increment's
+    maximum (the golden Q_5 minus droplet_init's Q0).  5 loops move Q ~ 18 by ~1e-4, so 1e-10 of
+    max|Q| lets a 2e-5 relative error of the mesh velocity pass; 1e-10 of max|dQ| does not.  The
+    fp64 reference's own increment is within 6e-11 of an extended-precision evaluation
+    (tests/test_oracle_droplet_grids.py)."""
+    q0 = load_golden("droplet_init")["Q0"]
+    dq = load_golden("droplet_pma")["Q_5"] - q0
+    return float(np.abs((Q.cpu().numpy() - q0) - dq).max() / np.abs(dq).max())
+
+
 @pytest.mark.parametrize("loops", [5, 400])
 def test_pma_loop(drop, loops):
     z = load_golden("droplet_pma")
     drop.pma(3e-9, loops)
     Q = drop.field("Q_val")
     assert _rel(Q, z[f"Q_{loops}"]) <= 1e-10
+    if loops == 5:
+        err = _increment_5(Q)
+        print(f"increment error {err:.3e}")
+        assert err <= 1e-10
 
 
 def test_two_full_steps(drop):
@@ -125,4 +140,8 @@ def test_global_memory_fallback(drop, monkeypatch):
     f = load_golden("droplet_fields")
     assert _rel(drop.residual(f["u1"], float(f["dt"])), f["R1"]) <= 1e-11
     drop.pma(3e-9, 5)
-    assert _rel(drop.field("Q_val"), load_golden("droplet_pma")["Q_5"]) <= 1e-10
+    Q = drop.field("Q_val")
+    assert _rel(Q, load_golden("droplet_pma")["Q_5"]) <= 1e-10
+    err = _increment_5(Q)
+    print(f"increment error {err:.3e}")
+    assert err <= 1e-10
