@@ -40,6 +40,10 @@ extern "C" {
  * struct.  3: nk_stats gained n_backtrack, step_min, n_device_steps (round 2); nk_sh_step_log. */
 #define NKHIP_ABI_VERSION 3
 
+/* Preconditioner of the inner LGMRES solve (scipy newton_krylov's inner_M, lgmres's M). */
+#define NK_PC_NONE 0     /* none: the solver as it is without this option */
+#define NK_PC_SPECTRAL 1 /* the exact inverse of the linear part I/k - L/2 of the SH Jacobian */
+
 #define NK_JVP_FD 0       /* KrylovJacobian.matvec finite difference (scipy-faithful) */
 #define NK_JVP_ANALYTIC 1 /* exact J v = v/k - (L v + (2 g u - 3 u^2) v)/2 */
 
@@ -156,6 +160,17 @@ int nk_sh_arnoldi_fused_edges(const double* const* V_dev, const double* const* E
  * consumer recompute (the path a missing neighbour takes).  Counts the fused launches, process-
  * wide, that ran with it (nx a multiple of the kernel's block width, >= 2 blocks per band). */
 int64_t nk_arnoldi_mbox_launches(void);
+
+/* z = M v = IFFT2( FFT2(v) / A0^ ), the inverse of A0 = I/k - L/2 (L as in nk_sh13_apply) on a
+ * periodic ny x nx grid, where A0 is diagonal in Fourier space: A0^(p,q) = 1/k - L^/2 with
+ * L^ = -s^2 - 2 s + (r-1), s = (2 cos(2 pi p/ny) + 2 cos(2 pi q/nx) - 4)/h^2.  The operator of
+ * NK_PC_SPECTRAL alone, as nk_sh13_apply is for L; replaces an `inner_M` a caller of
+ * scipy.optimize.newton_krylov (scipy/optimize/_nonlin.py:1463-1467) would build with
+ * scipy.fft.  Hand-written transforms, no FFT library.  nx, ny powers of two in [8, 4096] (they may
+ * differ), k > 0, k r < 2 (A0^ > 0), 16-B aligned vectors, z == v allowed; NK_EINVAL otherwise.
+ * Builds its tables and workspace per call and synchronises `stream` (a stepper keeps them). */
+int nk_sh_precond_apply(const double* v_dev, double* z_dev, int64_t ny, int64_t nx, double h,
+                        double r, double k, void* stream);
 
 /* ---------------- BLAS-1 (scipy get_blas_funcs dot/nrm2/axpy/scal in _gcrotmk.py:104-126) ------ */
 /* Scalar results are written to host memory; the call synchronises `stream`. */
@@ -324,6 +339,18 @@ int nk_sh_reset_profile(nk_sh* s);
  * to `steps` (host) and returns how many there were. */
 int nk_sh_step_log(nk_sh* s, double* steps, int32_t max);
 int64_t nk_sh_workspace_bytes(nk_sh* s);
+/* Preconditioner of the stepper's inner solves: scipy's `inner_M` (scipy/optimize/_nonlin.py:
+ * 1463-1467), which KrylovJacobian hands to lgmres as M (scipy/sparse/linalg/_isolve/lgmres.py:
+ * 166-177, _gcrotmk.py:112-121).  As there: the outer residual and the tolerance stay
+ * unpreconditioned, v0 = M F, and every Arnoldi vector is M (J z).  NK_PC_NONE restores the
+ * unpreconditioned solver exactly.  NK_PC_SPECTRAL (see nk_sh_precond_apply) needs a single slab
+ * (comm == NULL), nx and ny powers of two in [8, 4096] and k r < 2; NK_EINVAL otherwise, and the
+ * stepper stays as it was.  The first NK_PC_SPECTRAL builds the tables and takes two vectors of
+ * workspace (counted by nk_sh_workspace_bytes); no step allocates.  A preconditioned step runs
+ * the host loop: one JVP pass and one application of M per Arnoldi step, no fused step. */
+int nk_sh_set_precond(nk_sh* s, int32_t kind);
+/* Applications of M in the last nk_sh_step (0 without a preconditioner; -1: s == NULL). */
+int64_t nk_sh_precond_applies(nk_sh* s);
 
 /* ---------------- generic drop-in: newton_krylov(F, xin) over a device residual ---------------- */
 /* F(ctx, x_dev, f_dev, n) evaluates the residual on device buffers and returns 0 on success.
@@ -336,6 +363,16 @@ int64_t nk_solve_workspace_bytes(int64_t n, const nk_opts* opts);
 int nk_solve(nk_residual_fn F, void* ctx, const double* x0_dev, double* x_dev, int64_t n,
              const nk_opts* opts, nk_stats* stats, void* stream, void* workspace,
              int64_t workspace_bytes);
+
+/* nk_solve with the caller's preconditioner: M(ctx, in_dev, out_dev, n) writes out = M in with
+ * M ~ J^-1 on device buffers (in != out) and returns 0 on success -- scipy's `inner_M` as a
+ * callback (scipy/optimize/_nonlin.py:1463-1467; semantics as nk_sh_set_precond).  M == NULL
+ * behaves as nk_solve.  M's buffers, like F's, point into the workspace; with M the solver
+ * allocates one further vector itself. */
+typedef int (*nk_precond_fn)(void* ctx, const double* in_dev, double* out_dev, int64_t n);
+int nk_solve_m(nk_residual_fn F, nk_precond_fn M, void* ctx, const double* x0_dev, double* x_dev,
+               int64_t n, const nk_opts* opts, nk_stats* stats, void* stream, void* workspace,
+               int64_t workspace_bytes);
 
 /* ---------------- thin-film droplet on a moving mesh (python_work/droplet.py, config 3) -------- */
 /* Parameters = the module globals of droplet.py:22-53 (defaults from nk_drop_params_default). */

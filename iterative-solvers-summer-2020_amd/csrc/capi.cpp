@@ -739,7 +739,7 @@ int nk_sh_create(nk_sh** out, int64_t ny_local, int64_t nx, int64_t ny_global, d
                                    stencil_partial_slots(ny_local, nx));
   sh->E->sample = sh->opts.profile > 1 ? sh->opts.profile : 1;
   sh->P = std::make_unique<SHProblem>(*sh->E, ny_local, nx, ny_global, sh_coef(h, r, k, g),
-                                      sh->opts.jvp_mode);
+                                      sh->opts.jvp_mode, h, r);
   if (sh->P->status()) return sh->P->status();
   sh->NK = std::make_unique<NewtonKrylov>(*sh->E, *sh->P, sh->opts);
   if (sh->NK->status()) return sh->NK->status();
@@ -803,6 +803,31 @@ int nk_sh_step_log(nk_sh* s, double* steps, int32_t max) {
 
 int64_t nk_sh_workspace_bytes(nk_sh* s) { return s ? s->E->bytes_allocated() : -1; }
 
+int nk_sh_set_precond(nk_sh* s, int32_t kind) {
+  if (!s) return NK_EINVAL;
+  // a refusal allocates nothing and leaves the stepper as it was
+  int rc = s->P->set_precond(kind);
+  if (rc || kind == NK_PC_NONE) return rc;
+  rc = s->NK->prepare_precond();
+  if (rc) s->P->set_precond(NK_PC_NONE);
+  return rc;
+}
+
+int64_t nk_sh_precond_applies(nk_sh* s) { return s ? s->NK->precond_applies() : -1; }
+
+int nk_sh_precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
+                        double k, void* stream) {
+  if (!v || !z) return NK_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z)) & 15u) return NK_EINVAL;
+  FftPcPlan plan;
+  int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr);
+  if (rc) return rc;
+  hipError_t e = fftpc_apply(plan, v, z, S(stream));
+  if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
+  fftpc_destroy(&plan);
+  return hip_rc(e);
+}
+
 // ------------------------------------------------------------------------------ generic
 int64_t nk_solve_workspace_bytes(int64_t n, const nk_opts* opts) {
   if (n <= 0) return NK_EINVAL;
@@ -813,6 +838,12 @@ int64_t nk_solve_workspace_bytes(int64_t n, const nk_opts* opts) {
 int nk_solve(nk_residual_fn F, void* ctx, const double* x0, double* x, int64_t n,
              const nk_opts* opts, nk_stats* stats, void* stream, void* workspace,
              int64_t workspace_bytes) {
+  return nk_solve_m(F, nullptr, ctx, x0, x, n, opts, stats, stream, workspace, workspace_bytes);
+}
+
+int nk_solve_m(nk_residual_fn F, nk_precond_fn M, void* ctx, const double* x0, double* x,
+               int64_t n, const nk_opts* opts, nk_stats* stats, void* stream, void* workspace,
+               int64_t workspace_bytes) {
   if (!F || !x0 || !x || n <= 0) return NK_EINVAL;
   const nk_opts o = opts ? *opts : default_opts();
   if (o.jvp_mode != NK_JVP_FD) return NK_EINVAL;  // a user residual has no analytic Jacobian
@@ -825,11 +856,12 @@ int nk_solve(nk_residual_fn F, void* ctx, const double* x0, double* x, int64_t n
   if (!own && (workspace_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255u)))
     return NK_EINVAL;
   if (own && hipMalloc(reinterpret_cast<void**>(&ws), need) != hipSuccess) return NK_ENOMEM;
-  CallbackProblem P(E, F, ctx, ws + npad * nvec, ws + npad * (nvec + 1));
+  CallbackProblem P(E, F, ctx, ws + npad * nvec, ws + npad * (nvec + 1), M);
   int rc;
   {
     NewtonKrylov NK(E, P, o, ws, int64_t(sizeof(double)) * npad * nvec);
     rc = NK.status();
+    if (!rc && M) rc = NK.prepare_precond();
     if (!rc) rc = NK.solve(x0, x, stats);
   }
   hipStreamSynchronize(S(stream));

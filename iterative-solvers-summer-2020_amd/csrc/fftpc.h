@@ -1,0 +1,42 @@
+// Spectral preconditioner of the Swift-Hohenberg Newton-Krylov step (fftpc.hip):
+//   z = M v = IFFT2( FFT2(v) / A0^ ),  A0 = I/k - L/2 on a periodic ny x nx grid,
+// the exact inverse of the linear part of the Crank-Nicolson Jacobian (L the 13-point operator of
+// stencil.hip), diagonal in Fourier space:
+//   s(p,q) = (2 cos(2 pi p/ny) + 2 cos(2 pi q/nx) - 4)/h^2,  L^ = -s^2 - 2 s + (r - 1),
+//   A0^ = 1/k - L^/2.
+// No FFT library: three hand-written passes (rows real-to-complex, columns forward + symbol +
+// inverse on chip, rows complex-to-real), 48 B per grid point.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace nk {
+
+struct FftPcPlan {
+  int64_t ny = 0, nx = 0;
+  int ly = 0, lx2 = 0;       // log2(ny), log2(nx/2)
+  double ih2 = 0.0, r = 0.0, ik = 0.0;
+  double* tables = nullptr;  // twx (nx/2 complex: exp(-2 pi i j/nx)), then twy (ny/2 complex)
+  double* work = nullptr;    // the packed half spectrum: ny rows of nx/2 complex = ny*nx doubles
+  bool own_work = false;
+  int rows = 0;              // rows per block of the row passes
+  int cols = 0;              // columns per block of the column pass
+};
+
+// NK_OK when the spectral preconditioner exists for this grid and these constants: nx, ny powers
+// of two in [8, 4096], h > 0, k > 0 and k r < 2 (the symbol 1/k - L^/2 >= 1/k - r/2 + 1/2 is then
+// positive); NK_EINVAL otherwise.  Host only.
+int fftpc_check(int64_t ny, int64_t nx, double h, double r, double k);
+// Builds the twiddle tables on the host in long double and uploads them (synchronises).  `work`:
+// ny*nx doubles of device memory the plan uses as the half spectrum (nullptr: the plan allocates
+// and owns it).
+int fftpc_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, double k, double* work);
+void fftpc_destroy(FftPcPlan* p);
+// out = M in (three launches on s; in == out allowed; no synchronisation, no allocation).
+hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStream_t s);
+// algorithmic HBM bytes of one application
+inline double fftpc_bytes(int64_t ny, int64_t nx) { return 48.0 * double(ny) * double(nx); }
+
+}  // namespace nk

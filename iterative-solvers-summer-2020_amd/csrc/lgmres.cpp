@@ -1,6 +1,13 @@
 // LGMRES inner solve of the Newton-Krylov core: scipy/sparse/linalg/_isolve/lgmres.py:120-230
-// (x0 = 0, maxiter = 1, M = identity, prepend_outer_v = True, store_outer_Av = False) around the
+// (x0 = 0, maxiter = 1, prepend_outer_v = True, store_outer_Av = False) around the
 // FGMRES Arnoldi process of scipy/sparse/linalg/_isolve/_gcrotmk.py:14-180.
+//
+// Preconditioner (Problem::has_precond, scipy's inner_M = lgmres's M): as lgmres.py:166-177 and
+// _fgmres's lpsolve -- the outer residual and its norm stay unpreconditioned (so ptol is
+// unchanged), v0 = -M r_outer = M b, inner_res_0 = |v0|, and every Arnoldi vector is w = M (J z),
+// for the augmentation vectors too (they are stored without their A-image).  Such a call takes
+// the host loop only: one precond launch after each JVP, no fused step (the problem reports
+// none), no device-side control and no closing pass.
 //
 // Device/host split per Arnoldi step j -- one host synchronisation and ONE reduction (one
 // all-reduce on N GPUs) per step:
@@ -111,6 +118,11 @@ int NewtonKrylov::issue_step(int j, const double* z, double zs, double znorm, bo
     st_->njvp += 1;
   }
   if (rc) return rc;  // (w enters the update of the next fused step: the JVP wrote its edges)
+  if (P_.has_precond() && !(znorm == 0.0 && !have_w && !dev_scale)) {  // w = M (J z); M 0 = 0
+    rc = P_.precond(w, w);
+    if (rc) return rc;
+    npc_ += 1;
+  }
   st_->n_arnoldi += 1;
   // one pass: c_i = w.v_i (i <= j), Gram row v_j.v_i (i <= j, the diagonal is |v_j|^2), |w|^2
   VecList P;
@@ -140,9 +152,29 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
   const int m = o_.inner_m + n_o;
   const int64_t n = E_.n;
   const int K = int(outer_.size());
+  const bool pc = P_.has_precond();
+  if (pc && !MF_) return NK_EINVAL;  // prepare_precond() was not called
   const bool lag = lag_enabled() && P_.may_speculate();
-  const bool devctl = lag && devctl_enabled(E_.comm != nullptr || P_.prefers_devctl());
+  const bool devctl = !pc && lag && devctl_enabled(E_.comm != nullptr || P_.prefers_devctl());
   V_[0] = Fx_;  // v0 = b / |b|, kept raw with scale 1/|b|
+  double res0 = b_norm;  // inner_res_0 = |v0| before normalisation (lgmres.py:168)
+  if (pc) {  // v0 = M b (lgmres.py:166 with r_outer = -b), kept raw with scale 1/|M b|
+    int rc0 = P_.precond(Fx_, MF_);
+    if (rc0) return rc0;
+    npc_ += 1;
+    VecList none;
+    int64_t nb0 = 0;
+    rc0 = E_.launch(K_COMBO, 16.0 * n, [&] {
+      return combo_launch(MF_, MF_, 1.0, none, 0, n, E_.partial(), E_.s, &nb0);
+    });
+    double m2[2];
+    if (!rc0) rc0 = E_.reduce(nb0, 1, 2, m2);
+    if (rc0) return rc0;
+    res0 = std::sqrt(m2[0]);
+    if (!std::isfinite(res0)) return NK_NONFINITE;
+    if (res0 == 0.0) return NK_OK;  // scipy raises 'Preconditioner returned a zero vector'
+    V_[0] = MF_;
+  }
   // the loop state (shared with the device-side control: nk_kernels.h ArnCtlState)
   ArnCtlState& S = *hS_;
   S.m = m;
@@ -157,8 +189,8 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
   double* const wnorm = S.wnorm;
   double* const zs_ = S.zs;
   double* const h = S.h;
-  sig[0] = 1.0 / b_norm;
-  rn[0] = b_norm;
+  sig[0] = 1.0 / res0;
+  rn[0] = res0;
   double hcur[kMaxVec + 2];
   double red[2 * kMaxVec + 2];
   for (int i = 0; i < kMaxVec + 2; ++i) S.gv[i] = 0.0;
@@ -325,7 +357,7 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
             break;
           }
           if (i < j) {
-            C.cA[q] += b_norm * a[i] * zs_[i];
+            C.cA[q] += res0 * a[i] * zs_[i];
             C.cB[q] -= b[i] * zs_[i];
           } else {
             C.cB[q] += zs_[j];
@@ -486,7 +518,7 @@ int NewtonKrylov::lgmres(double tol, double* dnorm, double* dmax, double** dvec)
   double y[kMaxVec + 1];
   detail::lstsq_upper(S.R, j + 1, S.gv, y);
   for (int i = 0; i <= j; ++i) {
-    y[i] *= b_norm;  // y *= inner_res_0
+    y[i] *= res0;  // y *= inner_res_0
     if (!std::isfinite(y[i])) return NK_OK;
   }
   // -- dx = sum_i y_i z_i into the next outer slot (the oldest one if the ring is full; the

@@ -33,7 +33,7 @@ const char* kind_name(int kind) {
                                          "krylov_mdot", "krylov_combo", "reduce_final", "copy",
                                          "halo", "user_F", "axpby", "arnoldi_fused",
                                          "arnoldi_edge", "edge_gather", "arnoldi_slab_edges",
-                                         "arnoldi_ctl", "halo_push"};
+                                         "arnoldi_ctl", "halo_push", "sh_precond"};
   return (kind >= 0 && kind < K_NKINDS) ? names[kind] : "?";
 }
 
@@ -100,6 +100,7 @@ Engine::~Engine() {
     if (own_pool_ && pool_) hipFree(pool_);
     if (epool_) hipFree(epool_);
   }
+  for (double* p : aux_) hipFree(p);
   if (partial_) hipFree(partial_);
   if (dres_) hipFree(dres_);
   if (hres_) hipHostFree(hres_);
@@ -221,6 +222,22 @@ int Engine::alloc(int count, std::vector<double*>* out, void* external, int64_t 
   out->resize(count);
   for (int i = 0; i < count; ++i) (*out)[i] = pool_ + npad * i;
   pool_count_ = count;
+  return NK_OK;
+}
+
+int Engine::alloc_aux(int count, std::vector<double*>* out) {
+  const size_t bytes = sizeof(double) * size_t(npad) * size_t(count);
+  double* p = nullptr;
+  if (count < 1 || hipMalloc(reinterpret_cast<void**>(&p), bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return count < 1 ? NK_EINVAL : NK_ENOMEM;
+  }
+  aux_.push_back(p);
+  bytes_ += int64_t(bytes);
+  if (hipMemsetAsync(p, 0, bytes, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return NK_EHIP;
+  out->resize(count);
+  for (int i = 0; i < count; ++i) (*out)[i] = p + npad * i;
   return NK_OK;
 }
 
@@ -536,6 +553,15 @@ NewtonKrylov::~NewtonKrylov() {
   if (prm_) hipFree(prm_);
 }
 
+int NewtonKrylov::prepare_precond() {
+  if (init_status_) return init_status_;
+  if (MF_) return NK_OK;
+  std::vector<double*> v;
+  const int rc = E_.alloc_aux(1, &v);
+  if (!rc) MF_ = v[0];
+  return rc;
+}
+
 // NewtonKrylov::lgmres lives in lgmres.cpp
 
 int NewtonKrylov::line_search(double* s_out, double* fnorm_new, double* fmax, double* xmax) {
@@ -650,6 +676,7 @@ int NewtonKrylov::solve(const double* x_in, double* x_out, nk_stats* st) {
   std::memset(st_, 0, sizeof(nk_stats));
   st_->step_min = 1.0;
   steps_.clear();
+  npc_ = 0;
   ocount_ = 0;
   ohead_ = 0;
   const int64_t n = E_.n;

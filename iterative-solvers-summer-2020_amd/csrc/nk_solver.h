@@ -43,6 +43,7 @@ enum Kind : int {
   K_ARN_SLAB,
   K_CTL,
   K_PUSH,  // pushed halo rows of a producer (peer-memory slabs)
+  K_PRECOND,  // one application of the preconditioner (fftpc.hip's three passes, or a callback)
   K_NKINDS
 };
 
@@ -76,6 +77,10 @@ class Engine {
   int alloc(int count, std::vector<double*>* out, void* external = nullptr,
             int64_t external_bytes = 0);
   bool pool_chunk_mapped() const { return vmm_base_ != nullptr; }
+  // `count` further zeroed vectors of npad doubles outside the pool (no edge arrays, pool_index
+  // -1), owned by the engine and counted in bytes_allocated(): what an option set after
+  // construction needs (the preconditioner's workspace).  Synchronises.
+  int alloc_aux(int count, std::vector<double*>* out);
   // Edge arrays (nk_kernels.h, kEdgeW) of an ny x nx grid for the pool vectors.
   void enable_edges(int64_t ny, int64_t nx) {
     edge_ny_ = ny;
@@ -179,6 +184,7 @@ class Engine {
   void* vmm_base_ = nullptr;
   size_t vmm_size_ = 0, vmm_chunk_ = 0;
   std::vector<hipMemGenericAllocationHandle_t> vmm_h_;
+  std::vector<double*> aux_;  // alloc_aux allocations
   int vmm_alloc(size_t bytes, size_t chunk);
   void vmm_free();
   struct Pending {
@@ -237,6 +243,11 @@ struct Problem {
   // May the solver evaluate a JVP it later discards (the step after the last Arnoldi step)?  A
   // user callback must see exactly scipy's F calls, so the generic problem says no.
   virtual bool may_speculate() const { return true; }
+  // Preconditioner of the inner LGMRES solve (scipy's inner_M, lgmres.py's M): out = M in with
+  // M ~ J^-1, one launch sequence on the engine's stream; in == out is allowed.  With one, the
+  // solve takes the host-loop path only (no fused step, no device-side control, no closing pass).
+  virtual bool has_precond() const { return false; }
+  virtual int precond(const double* /*in*/, double* /*out*/) { return NK_EINVAL; }
   // Device-side Arnoldi control without a fused kernel (lgmres.cpp device_steps): w = J z with
   // the JVP's scale and FD step from the control's parameter block prm (nk_kernels.h kCtlPrm);
   // nothing when the step was handed back.  Problems whose Arnoldi steps are latency-bound
@@ -305,6 +316,11 @@ class NewtonKrylov {
   // Accepted Armijo step s of every Newton iteration of the last solve (scipy's
   // scalar_search_armijo result, _nonlin.py:294-314; 1 where no line search ran).
   const std::vector<double>& step_log() const { return steps_; }
+  // The vector a preconditioned solve needs beyond the pool (v0 = M F cannot alias F); called
+  // once when a preconditioner is first set, so that no solve allocates.
+  int prepare_precond();
+  // Applications of the preconditioner in the last solve.
+  int64_t precond_applies() const { return npc_; }
 
  private:
   int lgmres(double tol, double* dnorm, double* dmax, double** dvec);
@@ -331,6 +347,8 @@ class NewtonKrylov {
   double *X_ = nullptr, *Xt_ = nullptr, *Fx_ = nullptr, *Ft_ = nullptr, *G0_ = nullptr,
          *Gt_ = nullptr;
   double* Sv_ = nullptr;  // spare vector: target of the fused update (swapped into V_)
+  double* MF_ = nullptr;  // M F, the first basis vector of a preconditioned call (prepare_precond)
+  int64_t npc_ = 0;       // precond_applies()
   std::vector<double*> V_;      // V_[0] aliases Fx_ during a solve
   std::vector<double*> outer_;  // LGMRES augmentation ring
   std::vector<double> osig_, orn_;

@@ -13,8 +13,9 @@ namespace nk {
 // ============================================================================================
 // SHProblem
 // ============================================================================================
-SHProblem::SHProblem(Engine& E, int64_t ny, int64_t nx, int64_t ny_global, SHCoef c, int jvp_mode)
-    : E_(E), ny_(ny), nx_(nx), ny_g_(ny_global), c_(c), jvp_mode_(jvp_mode) {
+SHProblem::SHProblem(Engine& E, int64_t ny, int64_t nx, int64_t ny_global, SHCoef c, int jvp_mode,
+                     double h, double r)
+    : E_(E), ny_(ny), nx_(nx), ny_g_(ny_global), c_(c), jvp_mode_(jvp_mode), h_(h), r_(r) {
   // edge arrays for the fused Arnoldi kernel's block halos (1/64 of each pool vector)
   if (arnoldi_supported(1, ny, nx)) E_.enable_edges(ny, nx);
   // the fused kernel's mailbox, unless the slabs of several ranks share this device (their
@@ -87,6 +88,8 @@ SHProblem::SHProblem(Engine& E, int64_t ny, int64_t nx, int64_t ny_global, SHCoe
 
 SHProblem::~SHProblem() {
   if (slots_.mine) E_.comm->release_slots(this);
+  if (E_.s) hipStreamSynchronize(E_.s);
+  fftpc_destroy(&pc_);
   if (side_) hipStreamSynchronize(side_);
   if (B_) hipFree(B_);
   if (hx_) hipFree(hx_);
@@ -381,6 +384,7 @@ int SHProblem::jvp_dev(const double* x0, const double* G0, const double* z, cons
 // launch), exchanges them, then runs the fused pass with those rows as its halo.
 // NKHIP_FUSED=0 disables it (read per call, so a test can compare both paths in one process).
 bool SHProblem::has_fused(int nv) const {
+  if (pc_on_) return false;  // a preconditioned solve runs the host loop (M follows each JVP)
   const char* e = std::getenv("NKHIP_FUSED");
   if (e && e[0] == '0') return false;
   if (jvp_mode_ != NK_JVP_FD) return false;
@@ -573,6 +577,29 @@ int SHProblem::fused_step(const double* const* V, const double* c, int nv, const
   return rc;
 }
 
+int SHProblem::set_precond(int kind) {
+  if (kind == NK_PC_NONE) {
+    pc_on_ = false;
+    return NK_OK;
+  }
+  if (kind != NK_PC_SPECTRAL || dist() || ny_g_ != ny_) return NK_EINVAL;
+  if (fftpc_check(ny_, nx_, h_, r_, c_.k)) return NK_EINVAL;
+  if (!pc_.tables) {
+    std::vector<double*> w;
+    int rc = E_.alloc_aux(1, &w);
+    if (!rc) rc = fftpc_create(&pc_, ny_, nx_, h_, r_, c_.k, w[0]);
+    if (rc) return rc;
+  }
+  pc_on_ = true;
+  return NK_OK;
+}
+
+int SHProblem::precond(const double* in, double* out) {
+  if (!pc_on_) return NK_EINVAL;
+  return E_.launch(K_PRECOND, fftpc_bytes(ny_, nx_),
+                   [&] { return fftpc_apply(pc_, in, out, E_.s); });
+}
+
 void SHProblem::void_fused_steps(int count) {
   E_.void_last(K_ARNOLDI, count);
   if (dist() && edge_launched_) E_.void_last(K_ARN_EDGE, count);
@@ -615,8 +642,28 @@ EdgeOut SHProblem::edge_out(const double* v) {
 // ============================================================================================
 // CallbackProblem
 // ============================================================================================
-CallbackProblem::CallbackProblem(Engine& E, nk_residual_fn F, void* ctx, double* tmp, double* tmp2)
-    : E_(E), F_(F), ctx_(ctx), tmp_(tmp), tmp2_(tmp2) {}
+CallbackProblem::CallbackProblem(Engine& E, nk_residual_fn F, void* ctx, double* tmp, double* tmp2,
+                                 nk_precond_fn M)
+    : E_(E), F_(F), M_(M), ctx_(ctx), tmp_(tmp), tmp2_(tmp2) {}
+
+// The caller's M on device buffers.  The callback's buffers do not alias (an in-place request
+// reads a copy in tmp_, free between a JVP and the next one) and, like F's, lie in the workspace:
+// a result wanted elsewhere (v0, outside the pool) is written to tmp2_ and copied.
+int CallbackProblem::precond(const double* in, double* out) {
+  if (!M_) return NK_EINVAL;
+  const int64_t n = E_.n;
+  const double* src = in;
+  if (in == out) {
+    const int rc = E_.copy(tmp_, in, n);
+    if (rc) return rc;
+    src = tmp_;
+  }
+  double* dst = E_.pool_index(out) >= 0 ? out : tmp2_;
+  const int rc = E_.launch(K_PRECOND, 0.0, [&] {
+    return M_(ctx_, src, dst, n) == 0 ? hipSuccess : hipErrorUnknown;
+  });
+  return (rc || dst == out) ? rc : E_.copy(out, dst, n);
+}
 
 int CallbackProblem::norms(double* v, double* sum2, double* vmax) {
   VecList none;

@@ -2,6 +2,7 @@
 // and a generic device residual supplied through a C callback (the newton_krylov drop-in).
 #pragma once
 
+#include "fftpc.h"
 #include "nk_solver.h"
 
 namespace nk {
@@ -11,7 +12,8 @@ namespace nk {
 // hoisted once per time step (the reference recomputes L@Uo on every call).
 class SHProblem final : public Problem {
  public:
-  SHProblem(Engine& E, int64_t ny, int64_t nx, int64_t ny_global, SHCoef c, int jvp_mode);
+  SHProblem(Engine& E, int64_t ny, int64_t nx, int64_t ny_global, SHCoef c, int jvp_mode,
+            double h = 0.0, double r = 0.0);
   ~SHProblem() override;
   int status() const { return status_; }
   void set_jvp_mode(int m) { jvp_mode_ = m; }
@@ -38,6 +40,13 @@ class SHProblem final : public Problem {
   void set_edges(StencilArgs* A, const double* out);
   void side_edges(StencilArgs* A, const double* a, const double* b) const;
   void void_fused_steps(int count) override;
+  // NK_PC_NONE / NK_PC_SPECTRAL (fftpc.hip: the exact inverse of the Jacobian's linear part
+  // I/k - L/2).  Spectral: single slab only (no communicator), nx and ny powers of two in
+  // [8, 4096], k r < 2; NK_EINVAL otherwise, and the problem stays as it was.  The first call
+  // builds the tables and takes the workspace vector from the engine; later calls only switch.
+  int set_precond(int kind);
+  bool has_precond() const override { return pc_on_; }
+  int precond(const double* in, double* out) override;
 
  private:
   // any communicator (also a world of one: its halo is the periodic wrap through RCCL)
@@ -81,24 +90,31 @@ class SHProblem final : public Problem {
   std::vector<uint64_t> push_ep_;  // per pool vector: comm epoch of its last push (~0: none)
   const double* hxp_ = nullptr;  // the halo of the current x0 / direction (hx_ / hd_ or a slot)
   const double* hdp_ = nullptr;
+  double h_ = 0.0, r_ = 0.0;  // the grid spacing and r the coefficients were built from
+  FftPcPlan pc_{};            // spectral preconditioner (tables != nullptr once built)
+  bool pc_on_ = false;
 };
 
 // newton_krylov(F, xin) for an arbitrary device residual (droplet.py:383, PMA2_nk.py:100, ...):
 // the FD Jacobian of KrylovJacobian.matvec built from F evaluations.
 class CallbackProblem final : public Problem {
  public:
-  CallbackProblem(Engine& E, nk_residual_fn F, void* ctx, double* tmp, double* tmp2);
+  CallbackProblem(Engine& E, nk_residual_fn F, void* ctx, double* tmp, double* tmp2,
+                  nk_precond_fn M = nullptr);
   int64_t n_global() const override { return E_.n; }
   int eval(const double* x, const double* p, double alpha, double* xt, double* F, double* G,
            double red[3]) override;
   int jvp(const double* x0, const double* G0, const double* z, double zs, double sc,
           double* w) override;
   bool may_speculate() const override { return false; }  // scipy calls F exactly nfev + njvp times
+  bool has_precond() const override { return M_ != nullptr; }
+  int precond(const double* in, double* out) override;
 
  private:
   int norms(double* v, double* sum2, double* vmax);
   Engine& E_;
   nk_residual_fn F_;
+  nk_precond_fn M_;
   void* ctx_;
   double* tmp_;
   double* tmp2_;

@@ -30,6 +30,8 @@ NK_ENOMEM = -4
 ABI_VERSION = 3  # include/nkhip.h NKHIP_ABI_VERSION: the struct layouts below
 NK_JVP_FD = 0
 NK_JVP_ANALYTIC = 1
+NK_PC_NONE = 0
+NK_PC_SPECTRAL = 1
 
 
 class nk_opts(C.Structure):
@@ -85,6 +87,7 @@ class nk_stencil_pass(C.Structure):
 
 
 RESIDUAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
+PRECOND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 
 _P = C.c_void_p
 _D = C.c_double
@@ -105,6 +108,7 @@ SIGNATURES = [
     ("nk_sh_arnoldi_fused", C.c_int, [C.POINTER(_P), C.POINTER(_D), _I32, _P, _D, _P, _P, _P,
                                       _I64, _I64, _D, _D, _D, _D, _D, _D, _P, _P,
                                       C.POINTER(_D), _P]),
+    ("nk_sh_precond_apply", C.c_int, [_P, _P, _I64, _I64, _D, _D, _D, _P]),
     ("nk_edge_elems", C.c_int64, [_I64, _I64]),
     ("nk_arnoldi_mbox_launches", C.c_int64, []),
     ("nk_edge_gather", C.c_int, [_P, _P, _I64, _I64, _P]),
@@ -146,9 +150,13 @@ SIGNATURES = [
     ("nk_sh_reset_profile", C.c_int, [_P]),
     ("nk_sh_step_log", C.c_int, [_P, C.POINTER(_D), _I32]),
     ("nk_sh_workspace_bytes", C.c_int64, [_P]),
+    ("nk_sh_set_precond", C.c_int, [_P, _I32]),
+    ("nk_sh_precond_applies", C.c_int64, [_P]),
     ("nk_solve_workspace_bytes", C.c_int64, [_I64, C.POINTER(nk_opts)]),
     ("nk_solve", C.c_int, [RESIDUAL_FN, _P, _P, _P, _I64, C.POINTER(nk_opts),
                            C.POINTER(nk_stats), _P, _P, _I64]),
+    ("nk_solve_m", C.c_int, [RESIDUAL_FN, PRECOND_FN, _P, _P, _P, _I64, C.POINTER(nk_opts),
+                             C.POINTER(nk_stats), _P, _P, _I64]),
     ("nk_drop_params_default", C.c_int, [C.POINTER(nk_drop_params)]),
     ("nk_drop_create", C.c_int, [C.POINTER(_P), C.POINTER(nk_drop_params), C.POINTER(nk_opts),
                                  _P]),

@@ -62,6 +62,18 @@ def sh13_apply(v, h, r, ny=None, nx=None, out=None):
     return out
 
 
+def sh_precond(v, h, r, k, ny=None, nx=None, out=None):
+    """``M @ v`` with M the inverse of A0 = I/k - L/2 on the periodic grid, applied in Fourier
+    space where A0 is diagonal: the spectral ``inner_M`` of the Swift-Hohenberg step.  nx, ny powers
+    of two in [8, 4096], k r < 2; ``out`` may be ``v``."""
+    _dev(v, "v")
+    ny, nx = _grid(v, ny, nx)
+    out = torch.empty_like(v) if out is None else _dev(out, "out")
+    check(lib.nk_sh_precond_apply(_ptr(v), _ptr(out), ny, nx, float(h), float(r), float(k),
+                                  _stream()), "nk_sh_precond_apply")
+    return out
+
+
 def sh_residual(u, uo, h, r, k, g, ny=None, nx=None, out=None):
     """``residual(u)`` of sh_scipy_nk.py:47-49 with ``Uo = uo``, fused into one pass."""
     _dev(u, "u")

@@ -32,7 +32,7 @@ class SwiftHohenberg:
                  g: float = 1.0, *, ny: int | None = None, jvp: str = "fd", f_tol=None,
                  f_rtol=None, x_tol=None, x_rtol=None, maxiter=None, rdiff=None, outer_k=10,
                  inner_m=30, line_search="armijo", verbose=False, profile=False,
-                 comm=None, ny_local: int | None = None, stream=None):
+                 comm=None, ny_local: int | None = None, stream=None, inner_M=None):
         self.N = int(N)          # points in x (and in y unless ny is given)
         self.nx = int(N)
         self.ny = int(ny) if ny is not None else int(N)
@@ -55,6 +55,13 @@ class SwiftHohenberg:
                                self.k, self.g, C.byref(self.opts),
                                comm.handle if comm is not None else None, s), "nk_sh_create")
         self.last_stats = None
+        self.inner_M = None
+        if inner_M is not None:
+            try:
+                self.set_precond(inner_M)
+            except Exception:
+                self.close()
+                raise
 
     def _stream_ptr(self):
         st = self._stream if self._stream is not None else torch.cuda.current_stream()
@@ -76,6 +83,23 @@ class SwiftHohenberg:
         o = make_opts(**kw)
         check(lib.nk_sh_set_opts(self._h, C.byref(o)), "nk_sh_set_opts")
         self.opts = o
+
+    def set_precond(self, kind):
+        """Preconditioner of the inner LGMRES solves, scipy's ``inner_M``: ``None`` / ``"none"`` /
+        ``NK_PC_NONE`` (the unpreconditioned solver, exactly) or ``"spectral"`` /
+        ``NK_PC_SPECTRAL``, the exact inverse of the Jacobian's linear part I/k - L/2 applied with
+        hand-written FFT passes (``ops.sh_precond``).  Spectral needs a single slab (no ``comm``),
+        nx and ny powers of two in [8, 4096] and k r < 2; anything else raises and leaves the
+        stepper as it was."""
+        names = {None: _lib.NK_PC_NONE, "none": _lib.NK_PC_NONE, "spectral": _lib.NK_PC_SPECTRAL}
+        if isinstance(kind, str) or kind is None:
+            if kind not in names:
+                raise ValueError(f"inner_M={kind!r}: None or 'spectral'")
+            code = names[kind]
+        else:
+            code = int(kind)
+        check(lib.nk_sh_set_precond(self._h, code), "nk_sh_set_precond")
+        self.inner_M = "spectral" if code == _lib.NK_PC_SPECTRAL else None
 
     # ----------------------------------------------------------------------------- stepping
     def _as_grid(self, U):
@@ -111,6 +135,7 @@ class SwiftHohenberg:
         if mine != cur:
             cur.wait_stream(mine)
         self.last_stats = st.as_dict()
+        self.last_stats["n_precond"] = int(lib.nk_sh_precond_applies(self._h))
         if rc == _lib.NK_NO_CONVERGENCE:
             raise NoConvergence(out)
         raise_for_status(rc)

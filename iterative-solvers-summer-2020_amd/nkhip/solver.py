@@ -106,8 +106,8 @@ def newton_krylov(F, xin, iter=None, rdiff=None, method="lgmres", inner_maxiter=
     """Find a root of ``F`` with inexact Newton-Krylov on the GPU (scipy signature)."""
     if method != "lgmres":
         raise NotImplementedError("only method='lgmres' (the scipy default) is built")
-    if inner_M is not None or tol_norm is not None or iter is not None or callback is not None:
-        raise NotImplementedError("inner_M / tol_norm / iter / callback are not supported")
+    if tol_norm is not None or iter is not None or callback is not None:
+        raise NotImplementedError("tol_norm / iter / callback are not supported")
     inner_m = kw.pop("inner_inner_m", 30)
     if kw:
         raise ValueError(f"Unknown parameter {next(iter_keys(kw))}")
@@ -128,6 +128,7 @@ def newton_krylov(F, xin, iter=None, rdiff=None, method="lgmres", inner_maxiter=
     ws_al = ws[shift:]
     views = _Views(shape, n, [x0, x, ws_al])
     err = []
+    last = {"fp": 0, "x": None, "f": None, "told": True, "calls": 0}  # the latest F evaluation
 
     def _cb(_ctx, xp, fp, nn):
         try:
@@ -136,19 +137,61 @@ def newton_krylov(F, xin, iter=None, rdiff=None, method="lgmres", inner_maxiter=
             r = F(xv)
             r = torch.as_tensor(r, device="cuda", dtype=torch.float64)
             fv.copy_(r.reshape(shape))
+            if inner_M is not None:
+                last.update(fp=fp, x=xv, f=fv, told=False)
+                last["calls"] += 1
+                if last["calls"] == 1:  # F(xin): KrylovJacobian.setup
+                    last["told"] = True
+                    if hasattr(inner_M, "setup"):
+                        inner_M.setup(xv.clone(), fv.clone(), F)
             return 0
         except BaseException as e:  # noqa: BLE001 - re-raised after the C call returns
             err.append(e)
             return 1
 
+    # inner_M (scipy/optimize/_nonlin.py:1463-1467): a callable v -> M v with M ~ J^-1 on float64
+    # CUDA tensors shaped like xin (scipy takes a LinearOperator; its matvec is that callable),
+    # handed to the inner LGMRES as its preconditioner.  Its optional hooks are called as
+    # KrylovJacobian calls them: setup(x, f, func) once before the iteration, update(x, f) after
+    # every accepted Newton step (_nonlin.py:1515-1533).  The solver's iterates become visible to
+    # Python in F's evaluations: setup comes with the first one, and the iterate a step accepted is
+    # the latest evaluation when M is next applied to its residual (v0 = M F, the one application
+    # whose input is F's own output buffer) or when the solve returns.
+    mfn = _lib.PRECOND_FN(0)
+    if inner_M is not None:
+        matvec = inner_M if callable(inner_M) else getattr(inner_M, "matvec", None)
+        if matvec is None:
+            raise TypeError("inner_M must be callable or have a matvec method")
+
+        def _told():
+            if not last["told"]:
+                last["told"] = True
+                if hasattr(inner_M, "update"):
+                    inner_M.update(last["x"].clone(), last["f"].clone())
+
+        def _mcb(_ctx, ip, op, nn):
+            try:
+                if ip == last["fp"]:
+                    _told()
+                r = matvec(views.view(ip))
+                r = torch.as_tensor(r, device="cuda", dtype=torch.float64)
+                views.view(op).copy_(r.reshape(shape))
+                return 0
+            except BaseException as e:  # noqa: BLE001 - re-raised after the C call returns
+                err.append(e)
+                return 1
+
+        mfn = _lib.PRECOND_FN(_mcb)
     cfn = _lib.RESIDUAL_FN(_cb)
     st = _lib.nk_stats()
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rc = lib.nk_solve(cfn, None, C.c_void_p(x0.data_ptr()), C.c_void_p(x.data_ptr()), n,
-                      C.byref(o), C.byref(st), stream, C.c_void_p(ws_al.data_ptr()),
-                      ws_al.numel() * 8)
+    rc = lib.nk_solve_m(cfn, mfn, None, C.c_void_p(x0.data_ptr()), C.c_void_p(x.data_ptr()), n,
+                        C.byref(o), C.byref(st), stream, C.c_void_p(ws_al.data_ptr()),
+                        ws_al.numel() * 8)
     if err:
         raise err[0]
+    if inner_M is not None and rc in (_lib.NK_OK, _lib.NK_NO_CONVERGENCE):
+        _told()  # the last accepted step
     out = x.cpu().numpy().reshape(np.shape(xin)) if as_numpy else x.reshape(shape)
     if rc == _lib.NK_NO_CONVERGENCE:
         raise NoConvergence(out)
