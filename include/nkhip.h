@@ -437,6 +437,34 @@ int nk_shlin_create(nk_shlin** out, int64_t ny, int64_t nx, double h, double r, 
 int nk_shlin_destroy(nk_shlin* s);
 int nk_shlin_step(nk_shlin* s, const double* U_dev, const double* Uo_dev, double* Unew_dev,
                   int64_t* iters, double* relres);
+/* Preconditioner of the stepper's CG solve.  NK_PC_NONE restores the unpreconditioned stepper
+ * exactly.  NK_PC_SPECTRAL: preconditioned CG with the constant-coefficient part of the matrix,
+ *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean(D), 0)  (recomputed every step),
+ * applied in Fourier space by the passes of nk_sh_precond_apply; the stopping rule is unchanged
+ * (the recursive unpreconditioned residual).  Needs nx and ny powers of two in [8, 4096] and
+ * k r < 2; NK_EINVAL otherwise, and the stepper stays as it was.  The first NK_PC_SPECTRAL builds
+ * the tables and takes two vectors of workspace; no step allocates. */
+int nk_shlin_set_precond(nk_shlin* s, int32_t kind);
+/* Applications of M launched in the last nk_shlin_step (iterations + 1: the one of the start, and
+ * the last iteration's, queued before its residual is known; 0 without M; -1: s == NULL). */
+int64_t nk_shlin_precond_applies(nk_shlin* s);
+/* sigma of the last nk_shlin_step (0 without M). */
+double nk_shlin_precond_shift(nk_shlin* s);
+/* z = M v, M = ((1 + sigma) I - (k/2) L)^-1 on a periodic ny x nx grid: the operator of the
+ * stepper's NK_PC_SPECTRAL alone, as nk_sh_precond_apply is (this is its ik = (1 + sigma)/k, times
+ * 1/k).  sigma >= 0; grid, alignment and k r < 2 as there; z == v allowed.  w and dot_host are given
+ * together or both NULL: with them the last FFT pass also forms the block sums of w_i z_i, added
+ * in a fixed order into *dot_host = w . z (host memory; the same bits on every call); z is the same
+ * either way.  Builds its tables and workspace per call and synchronises `stream`. */
+int nk_shlin_precond_apply(const double* v_dev, double* z_dev, int64_t ny, int64_t nx, double h,
+                           double r, double k, double sigma, const double* w_dev,
+                           double* dot_host, void* stream);
+/* HIP-event time of one nk_shlin_precond_apply's three passes on a zero field, in milliseconds,
+ * without (*ms_plain) and with (*ms_dot) the fused dot: `reps` >= 1 applications between two
+ * events after one untimed application, tables and workspace built outside the timed region.
+ * Synchronises `stream`.  Diagnostic only (scripts/shlin_precond_probe.py). */
+int nk_debug_shlin_precond_time(int64_t ny, int64_t nx, double h, double r, double k, double sigma,
+                                int32_t reps, double* ms_plain, double* ms_dot, void* stream);
 
 /* ---------------- MEMS on a moving mesh (python_work/PMA2_nk.py) ------------ */
 /* u_t = -(-Lap)^2 u - lambda/(1+u)^2 + lambda eps^(m-2)/(1+u)^m on [endl, endr]^2 (N x N), one

@@ -1009,6 +1009,82 @@ int nk_shlin_step(nk_shlin* s, const double* U, const double* Uo, double* Unew, 
   if (relres) *relres = st.relres;
   return rc;
 }
+int nk_shlin_set_precond(nk_shlin* s, int32_t kind) {
+  if (!s) return NK_EINVAL;
+  return reinterpret_cast<ShLinStepper*>(s)->set_precond(kind);
+}
+int64_t nk_shlin_precond_applies(nk_shlin* s) {
+  return s ? reinterpret_cast<ShLinStepper*>(s)->last().precond_applies : -1;
+}
+double nk_shlin_precond_shift(nk_shlin* s) {
+  return s ? reinterpret_cast<ShLinStepper*>(s)->last().shift : -1.0;
+}
+
+int nk_shlin_precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
+                           double k, double sigma, const double* w, double* dot_host,
+                           void* stream) {
+  if (!v || !z || (w == nullptr) != (dot_host == nullptr)) return NK_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z) |
+       reinterpret_cast<uintptr_t>(w)) & 15u)
+    return NK_EINVAL;
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return NK_EINVAL;
+  FftPcPlan plan;
+  int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr);
+  if (rc) return rc;
+  double* red = nullptr;  // the block partials, then the sum
+  const int64_t nb = fftpc_dot_blocks(plan);
+  hipError_t e = hipSuccess;
+  if (w) e = hipMalloc(reinterpret_cast<void**>(&red), sizeof(double) * size_t(nb + 1));
+  int64_t nblk = 0;
+  if (e == hipSuccess)
+    e = fftpc_apply_shift(plan, v, z, (1.0 + sigma) / k, 1.0 / k, w, red, &nblk, S(stream));
+  if (e == hipSuccess && w)
+    e = reduce_final_launch(red, nblk, 1, 1, red + nb, nullptr, S(stream));
+  if (e == hipSuccess && w)
+    e = hipMemcpyAsync(dot_host, red + nb, sizeof(double), hipMemcpyDeviceToHost, S(stream));
+  if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
+  if (red) hipFree(red);
+  fftpc_destroy(&plan);
+  return hip_rc(e);
+}
+
+int nk_debug_shlin_precond_time(int64_t ny, int64_t nx, double h, double r, double k, double sigma,
+                                int32_t reps, double* ms_plain, double* ms_dot, void* stream) {
+  if (reps < 1 || !ms_plain || !ms_dot || !(sigma >= 0.0) || !std::isfinite(sigma))
+    return NK_EINVAL;
+  FftPcPlan plan;
+  int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr);
+  if (rc) return rc;
+  const size_t n = size_t(ny * nx);
+  const int64_t nb = fftpc_dot_blocks(plan);
+  double* buf = nullptr;  // v, z, then the block partials
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), sizeof(double) * (2 * n + size_t(nb)));
+  if (e == hipSuccess) e = hipMemsetAsync(buf, 0, sizeof(double) * (2 * n + size_t(nb)), S(stream));
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  double* out[2] = {ms_plain, ms_dot};
+  for (int leg = 0; leg < 2 && e == hipSuccess; ++leg) {
+    const double* w = leg ? buf : nullptr;
+    double* part = leg ? buf + 2 * n : nullptr;
+    // one untimed application first (code object load, caches), then reps between two events
+    for (int i = 0; i <= reps && e == hipSuccess; ++i) {
+      if (i == 1) e = hipEventRecord(ev[0], S(stream));
+      if (e == hipSuccess)
+        e = fftpc_apply_shift(plan, buf, buf + n, (1.0 + sigma) / k, 1.0 / k, w, part, nullptr,
+                              S(stream));
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], S(stream));
+    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    *out[leg] = double(ms) / reps;
+  }
+  for (int i = 0; i < 2; ++i)
+    if (ev[i]) hipEventDestroy(ev[i]);
+  if (buf) hipFree(buf);
+  fftpc_destroy(&plan);
+  return hip_rc(e);
+}
 
 // ------------------------------------------------------------------------------ PMA2 (MEMS)
 int nk_mems_params_default(nk_mems_params* p) {

@@ -36,7 +36,21 @@ int fftpc_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, doubl
 void fftpc_destroy(FftPcPlan* p);
 // out = M in (three launches on s; in == out allowed; no synchronisation, no allocation).
 hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStream_t s);
-// algorithmic HBM bytes of one application
+// The same passes with the symbol's constants given per application: out = scale * (ik I - L/2)^-1
+// in (fftpc_apply is ik = 1/k, scale = 1, in the plan's own arithmetic).  A shifted operator
+// ((1 + sigma) I - (k/2) L)^-1 is ik = (1 + sigma)/k, scale = 1/k; ik > (r - 1)/2 keeps the symbol
+// positive.  The tables do not depend on ik: no plan rebuild, no allocation, no synchronisation.
+// With w (16-B aligned; may be `in` or `out`), the last pass also multiplies every value it stores
+// by the matching entry of w and leaves one partial sum per block in partial[0, *nblk)
+// (fftpc_dot_blocks(p) <= 4096 values); summed in order (reduce_final_launch) they give w . out,
+// bit-reproducibly.  w and partial are given together or not at all.
+hipError_t fftpc_apply_shift(const FftPcPlan& p, const double* in, double* out, double ik,
+                             double scale, const double* w, double* partial, int64_t* nblk,
+                             hipStream_t s);
+// blocks of a row pass = partial sums of an application with the dot
+inline int64_t fftpc_dot_blocks(const FftPcPlan& p) { return p.rows > 0 ? p.ny / p.rows : 0; }
+// algorithmic HBM bytes of one application (fftpc_dot_bytes: the last pass also reads w)
 inline double fftpc_bytes(int64_t ny, int64_t nx) { return 48.0 * double(ny) * double(nx); }
+inline double fftpc_dot_bytes(int64_t ny, int64_t nx) { return 56.0 * double(ny) * double(nx); }
 
 }  // namespace nk

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/nkhip.h"
+#include "nk_device.h"
 
 namespace nk {
 
@@ -215,6 +216,53 @@ __global__ __launch_bounds__(kRowThreads) void fftpc_rows_inv(const cd* __restri
   for (int idx = threadIdx.x; idx < total; idx += blockDim.x) dst[idx] = buf[idx];
 }
 
+// Pass 3 with the dot product w . out: the same pass, and every value about to be stored is also
+// multiplied by the matching entry of w; a thread sums its products in store order, the block in
+// block_reduce's fixed tree, and partial[blockIdx.x] receives the block's sum (reduce_final then
+// adds the blocks in a fixed order: the dot is deterministic).  8 B per point more than the pass
+// alone, against 16 for a separate dot pass.  w may be `out` or the vector the application
+// started from (each entry is read by the thread that then overwrites it): no __restrict__.
+__global__ __launch_bounds__(kRowThreads) void fftpc_rows_inv_dot(const cd* __restrict__ H,
+                                                                  double* out, int nx, int lx2,
+                                                                  int rows,
+                                                                  const cd* __restrict__ twx,
+                                                                  const double* w,
+                                                                  double* __restrict__ partial) {
+  cd* buf = fft_lds;
+  const int n2 = nx >> 1;
+  const int64_t row0 = int64_t(blockIdx.x) * rows;
+  const int per = (n2 >> 1) + 1;
+  for (int idx = threadIdx.x; idx < rows * per; idx += blockDim.x) {
+    const int b = idx / per, k = idx - b * per;
+    cd* z = buf + (b << lx2);
+    const cd* src = H + (row0 + b) * n2;
+    if (k == 0) {
+      const cd x0 = src[0];
+      z[0] = cd{x0.x + x0.y, x0.x - x0.y};
+      continue;
+    }
+    const int m = n2 - k;
+    const cd xk = src[k], xm = src[m];
+    const cd E = cd{xk.x + xm.x, xk.y - xm.y};
+    const cd O = cmulc(cd{xk.x - xm.x, xk.y + xm.y}, twx[k]);
+    z[brev(k, lx2)] = cd{E.x - O.y, E.y + O.x};
+    if (m != k) z[brev(m, lx2)] = cd{E.x + O.y, O.x - E.y};
+  }
+  __syncthreads();
+  fft_inv(buf, lx2, rows, twx, 2);
+  cd* dst = reinterpret_cast<cd*>(out) + row0 * n2;
+  const cd* wv = reinterpret_cast<const cd*>(w) + row0 * n2;
+  const int total = rows * n2;
+  double acc[1] = {0.0};
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const cd zv = buf[idx], ww = wv[idx];
+    acc[0] += ww.x * zv.x + ww.y * zv.y;
+    dst[idx] = zv;
+  }
+  const double v = block_reduce<1, 1, kRowThreads>(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = v;
+}
+
 struct Symbol {
   double ih2, r, ik, scale;
   // scale / A0^ from the two cosines
@@ -369,7 +417,12 @@ void fftpc_destroy(FftPcPlan* p) {
   *p = FftPcPlan{};
 }
 
-hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStream_t s) {
+namespace {
+// The three passes with the symbol's constants given: out = IFFT2(FFT2(in) * scale / (ik - L^/2))
+// (scale includes the transforms' 1/(nx ny)); with w, the last pass also leaves the block
+// partials of w . out.
+hipError_t apply_passes(const FftPcPlan& p, const double* in, double* out, double ik, double scale,
+                        const double* w, double* partial, hipStream_t s) {
   if (!p.tables || !p.work || !in || !out || in == p.work || out == p.work)
     return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u)
@@ -381,14 +434,34 @@ hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStr
   const size_t row_lds = sizeof(cd) * size_t(p.rows) * size_t(n2);
   const size_t col_lds = sizeof(cd) * size_t(ny) * size_t(p.cols);
   const int col_threads = std::min(kColThreadsMax, std::max(64, (ny * p.cols) / 4));
-  Symbol sym{p.ih2, p.r, p.ik, 1.0 / (double(nx) * double(ny))};
+  Symbol sym{p.ih2, p.r, ik, scale};
   fftpc_rows_fwd<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(in, H, nx, p.lx2, p.rows,
                                                                       twx);
   fftpc_cols<<<dim3(n2 / p.cols), dim3(col_threads), col_lds, s>>>(H, ny, n2, p.ly,
                                                                   ilog2(p.cols), twy, twx, sym);
-  fftpc_rows_inv<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(H, out, nx, p.lx2, p.rows,
-                                                                      twx);
+  if (w)
+    fftpc_rows_inv_dot<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(
+        H, out, nx, p.lx2, p.rows, twx, w, partial);
+  else
+    fftpc_rows_inv<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(H, out, nx, p.lx2,
+                                                                        p.rows, twx);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStream_t s) {
+  return apply_passes(p, in, out, p.ik, 1.0 / (double(p.nx) * double(p.ny)), nullptr, nullptr, s);
+}
+
+hipError_t fftpc_apply_shift(const FftPcPlan& p, const double* in, double* out, double ik,
+                             double scale, const double* w, double* partial, int64_t* nblk,
+                             hipStream_t s) {
+  if (!(ik > 0.5 * (p.r - 1.0)) || !std::isfinite(ik) || !std::isfinite(scale))
+    return hipErrorInvalidValue;  // the symbol ik - L^/2 >= ik - (r - 1)/2 must stay positive
+  if ((w == nullptr) != (partial == nullptr) || (w && w == p.work)) return hipErrorInvalidValue;
+  if (reinterpret_cast<uintptr_t>(w) & 15u) return hipErrorInvalidValue;
+  if (nblk) *nblk = fftpc_dot_blocks(p);
+  return apply_passes(p, in, out, ik, scale / (double(p.nx) * double(p.ny)), w, partial, s);
 }
 
 }  // namespace nk

@@ -376,6 +376,23 @@ __global__ void __launch_bounds__(256) shlin_diag_kernel(const double* U, const 
   d[i] = a * a * k / 16 - g * k * U[i];
 }
 
+// The same D with the per-block sum of its entries (the preconditioned stepper's shift is their
+// mean).  Grid-stride, one partial per block, as cg_update_kernel.
+__global__ __launch_bounds__(256) void shlin_diag_sum_kernel(const double* U, const double* Uo,
+                                                             double k, double g, double* d,
+                                                             int64_t n, double* partial) {
+  double acc[1] = {0.0};
+  const int64_t stride = int64_t(gridDim.x) * 256;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) {
+    const double a = 5 * U[i] - Uo[i];
+    const double v = a * a * k / 16 - g * k * U[i];
+    d[i] = v;
+    acc[0] += v;
+  }
+  const double v = block_reduce<1, 1, 256>(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = v;
+}
+
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // vectors of at most this many 2048-element chunks take the latency-bound variants (the
@@ -590,6 +607,17 @@ hipError_t shlin_diag_launch(const double* U, const double* Uo, double k, double
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(shlin_diag_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, U, Uo, k,
                      g, d, n);
+  return hipGetLastError();
+}
+
+hipError_t shlin_diag_sum_launch(const double* U, const double* Uo, double k, double g, double* d,
+                                 int64_t n, double* partial, hipStream_t s, int64_t* nblk) {
+  int64_t b = (n + 255) / 256;
+  if (b > 1024) b = 1024;
+  if (b < 1) b = 1;
+  *nblk = b;
+  hipLaunchKernelGGL(shlin_diag_sum_kernel, dim3(unsigned(b)), dim3(256), 0, s, U, Uo, k, g, d, n,
+                     partial);
   return hipGetLastError();
 }
 

@@ -183,6 +183,10 @@ hipError_t cg_update_launch(double* x, double* r, const double* p, const double*
 // d = (5U - Uo)^2 k/16 - g k U (sh_linearised.py:50)
 hipError_t shlin_diag_launch(const double* U, const double* Uo, double k, double g, double* d,
                              int64_t n, hipStream_t s);
+// The same d, and partial[0..*nblk) = per-block sums of d (*nblk <= 1024): the mean of D is the
+// shift of the preconditioned stepper (shlin.cpp).
+hipError_t shlin_diag_sum_launch(const double* U, const double* Uo, double k, double g, double* d,
+                                 int64_t n, double* partial, hipStream_t s, int64_t* nblk);
 // dst = src, streamed in 16-KB chunks per block (the bench's per-box bandwidth probe); n even,
 // 16-B aligned
 hipError_t stream_copy_launch(const double* src, double* dst, int64_t n, hipStream_t s);

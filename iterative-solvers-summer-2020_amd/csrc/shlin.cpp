@@ -2,6 +2,8 @@
 // gradients with the operator applied matrix-free by the 13-point stencil (SMode::LINOP, which
 // also forms the new search direction p = r + beta p_old on the fly and the fused p.Ap), plus a
 // fused x/r update with r.r: two passes (88 B/point) and two scalar read-backs per iteration.
+// With set_precond(NK_PC_SPECTRAL) (shlin.h) an application of the spectral preconditioner follows
+// each update (56 B/point more), its last pass returning r.z.
 #include "shlin.h"
 
 #include <cmath>
@@ -10,8 +12,8 @@ namespace nk {
 
 ShLinStepper::ShLinStepper(int64_t ny, int64_t nx, double h, double r, double g, double k,
                            double rtol, int64_t maxiter, hipStream_t s, bool profile)
-    : E(ny * nx, nullptr, s, profile, stencil_partial_slots(ny, nx)), ny_(ny), nx_(nx), g_(g),
-      k_(k), rtol_(rtol), maxiter_(maxiter) {
+    : E(ny * nx, nullptr, s, profile, stencil_partial_slots(ny, nx)), ny_(ny), nx_(nx), h_(h),
+      r_(r), g_(g), k_(k), rtol_(rtol), maxiter_(maxiter) {
   c_ = sh_coef(h, r, k, g);
   status_ = E.alloc(8, &v_);
 }
@@ -34,8 +36,123 @@ int ShLinStepper::linop(const double* a, const double* b, double beta, const dou
                   [&] { return stencil_launch(SMode::LINOP, A, E.s, nblk); });
 }
 
+ShLinStepper::~ShLinStepper() { fftpc_destroy(&pc_); }
+
+int ShLinStepper::set_precond(int kind) {
+  if (status_) return status_;
+  if (kind == NK_PC_NONE) {
+    pc_on_ = false;
+    return NK_OK;
+  }
+  if (kind != NK_PC_SPECTRAL) return NK_EINVAL;
+  // a refusal allocates nothing and leaves the stepper as it was
+  if (fftpc_check(ny_, nx_, h_, r_, k_)) return NK_EINVAL;
+  if (!pc_.tables) {
+    // the last FFT pass leaves one partial per block: at most 4096 (nx = 4096, one row each)
+    if (E.partial_cap() < 4096) return NK_EINVAL;
+    if (!z_) {  // z and, behind it, the half spectrum
+      std::vector<double*> w;
+      const int rc = E.alloc_aux(2, &w);
+      if (rc) return rc;
+      z_ = w[0];
+    }
+    const int rc = fftpc_create(&pc_, ny_, nx_, h_, r_, k_, z_ + E.npad);
+    if (rc) return rc;
+  }
+  pc_on_ = true;
+  return NK_OK;
+}
+
+int ShLinStepper::precond(const double* r, double* z, double sigma, int64_t* nblk) {
+  // ((1 + sigma) I - L k/2)^-1 = (1/k) (I (1 + sigma)/k - L/2)^-1
+  return E.launch(K_PRECOND, fftpc_dot_bytes(ny_, nx_), [&] {
+    return fftpc_apply_shift(pc_, r, z, (1.0 + sigma) / k_, 1.0 / k_, r, E.partial(), nblk, E.s);
+  });
+}
+
+// The step with M: as step() below, with z = M r in the place of r in the search direction and
+// rho = r.z in the place of r.r in alpha and beta; the stop still tests r.r.
+int ShLinStepper::step_pcg(const double* U, const double* Uo, double* Unew, ShLinStats* st) {
+  const int64_t n = E.n;
+  double *x = v_[0], *r = v_[1], *p = v_[2], *pn = v_[3], *q = v_[4], *d = v_[5], *zero = v_[6],
+         *b = v_[7], *z = z_;
+  constexpr int kSlotAux = Engine::kSlotCombo;  // a result read together with the next reduce()
+  int64_t nblk = 0, napp = 0;
+  double red[3];
+  last_ = ShLinStats{};
+  int rc = E.launch(K_AXPBY, 24.0 * n, [&] {
+    return shlin_diag_sum_launch(U, Uo, k_, g_, d, n, E.partial(), E.s, &nblk);
+  });
+  if (!rc) rc = E.reduce_async(nblk, 1, 1, kSlotAux);  // sum D, read after the next reduce()
+  if (!rc) rc = linop(U, U, 0.0, zero, -k_ / 2, pn, b, &nblk);
+  VecList none{};
+  if (!rc) rc = E.launch(K_COMBO, 16.0 * n, [&] {
+    return combo_launch(b, b, 1.0, none, 0, n, E.partial(), E.s, &nblk);
+  });
+  if (!rc) rc = E.reduce(nblk, 1, 2, red);
+  if (rc) return rc;
+  const double bnorm = std::sqrt(red[0]);
+  const double dmean = *E.hres(kSlotAux) / double(n);
+  if (!std::isfinite(dmean)) return NK_NONFINITE;
+  const double sigma = dmean > 0.0 ? dmean : 0.0;
+  last_.shift = sigma;
+  if (st) *st = last_;
+  // warm start x = U: r = b - A U, z = M r
+  rc = E.copy(x, U, n);
+  if (!rc) rc = linop(U, U, 0.0, d, k_ / 2, pn, q, &nblk);
+  VecList mq{};
+  mq.p[0] = q;
+  mq.c[0] = -1.0;
+  if (!rc) rc = E.launch(K_COMBO, 24.0 * n, [&] {
+    return combo_launch(r, b, 1.0, mq, 1, n, E.partial(), E.s, &nblk);
+  });
+  if (!rc) rc = E.reduce_async(nblk, 1, 1, kSlotAux);
+  if (!rc) rc = precond(r, z, sigma, &nblk);
+  ++napp;
+  if (!rc) rc = E.reduce(nblk, 1, 1, red);
+  if (rc) return rc;
+  double rr = *E.hres(kSlotAux), rho = red[0];
+  const double stop = rtol_ * bnorm;
+  double beta = 0.0;
+  int64_t it = 0;
+  while (std::sqrt(rr) > stop && it < maxiter_) {
+    if (!(rho > 0.0)) return NK_NONFINITE;  // M is positive definite: non-finite data
+    // p' = z + beta p; q = A p'; p'.q
+    rc = linop(z, it == 0 ? z : p, beta, d, k_ / 2, pn, q, &nblk);
+    if (!rc) rc = E.reduce(nblk, 1, 3, red);
+    if (rc) return rc;
+    const double pq = red[0];
+    if (!(pq > 0.0)) return NK_NONFINITE;  // not SPD (g k U dominated) or non-finite data
+    const double alpha = rho / pq;
+    rc = E.launch(K_AXPBY, 48.0 * n, [&] {
+      return cg_update_launch(x, r, pn, q, alpha, n, E.partial(), E.s, &nblk);
+    });
+    if (!rc) rc = E.reduce_async(nblk, 1, 1, kSlotAux);
+    // queued behind the update: r.r and r.z come back together
+    if (!rc) rc = precond(r, z, sigma, &nblk);
+    ++napp;
+    if (!rc) rc = E.reduce(nblk, 1, 1, red);
+    if (rc) return rc;
+    rr = *E.hres(kSlotAux);
+    beta = red[0] / rho;
+    rho = red[0];
+    std::swap(p, pn);
+    ++it;
+  }
+  rc = E.copy(Unew, x, n);
+  if (!rc) rc = E.sync();
+  last_.iters = it;
+  last_.relres = bnorm > 0 ? std::sqrt(rr) / bnorm : std::sqrt(rr);
+  last_.precond_applies = napp;
+  if (st) *st = last_;
+  if (rc) return rc;
+  return std::isfinite(rr) ? (std::sqrt(rr) <= stop ? NK_OK : NK_NO_CONVERGENCE) : NK_NONFINITE;
+}
+
 int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinStats* st) {
   if (status_) return status_;
+  if (pc_on_) return step_pcg(U, Uo, Unew, st);
+  last_ = ShLinStats{};
   const int64_t n = E.n;
   double *x = v_[0], *r = v_[1], *p = v_[2], *pn = v_[3], *q = v_[4], *d = v_[5], *zero = v_[6],
          *b = v_[7];
@@ -87,10 +204,9 @@ int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinSta
   }
   rc = E.copy(Unew, x, n);
   if (!rc) rc = E.sync();
-  if (st) {
-    st->iters = it;
-    st->relres = bnorm > 0 ? std::sqrt(rr) / bnorm : std::sqrt(rr);
-  }
+  last_.iters = it;
+  last_.relres = bnorm > 0 ? std::sqrt(rr) / bnorm : std::sqrt(rr);
+  if (st) *st = last_;
   if (rc) return rc;
   return std::isfinite(rr) ? (std::sqrt(rr) <= stop ? NK_OK : NK_NO_CONVERGENCE) : NK_NONFINITE;
 }

@@ -11,7 +11,7 @@ from .dist import PeerComm, RcclComm, loopback_comms, neighbours, peer_comms, sl
 from .droplet import Droplet, read_init, write_init  # noqa: F401
 from .mems import Mems  # noqa: F401
 from .ops import (axpy, dot, lap5_apply, maxnorm, maxpy, mdot, nrm2, scal, sh13_apply, stream_copy,  # noqa: F401
-                  sh_arnoldi_fused, edge_gather, arnoldi_mbox_launches, sh_fdjvp, sh_jvp, sh_precond, sh_residual)
+                  sh_arnoldi_fused, edge_gather, arnoldi_mbox_launches, sh_fdjvp, sh_jvp, sh_precond, sh_residual, shlin_precond)
 from .sh import SwiftHohenberg, sh_step  # noqa: F401
 from .shlin import SHLinearised  # noqa: F401
 from .solver import NoConvergence, newton_krylov  # noqa: F401

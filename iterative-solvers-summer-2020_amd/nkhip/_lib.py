@@ -176,6 +176,13 @@ SIGNATURES = [
     ("nk_shlin_create", C.c_int, [C.POINTER(_P), _I64, _I64, _D, _D, _D, _D, _D, _I64, _P]),
     ("nk_shlin_destroy", C.c_int, [_P]),
     ("nk_shlin_step", C.c_int, [_P, _P, _P, _P, C.POINTER(_I64), C.POINTER(_D)]),
+    ("nk_shlin_set_precond", C.c_int, [_P, _I32]),
+    ("nk_shlin_precond_applies", C.c_int64, [_P]),
+    ("nk_shlin_precond_shift", C.c_double, [_P]),
+    ("nk_shlin_precond_apply", C.c_int, [_P, _P, _I64, _I64, _D, _D, _D, _D, _P, C.POINTER(_D),
+                                         _P]),
+    ("nk_debug_shlin_precond_time", C.c_int, [_I64, _I64, _D, _D, _D, _D, _I32, C.POINTER(_D),
+                                              C.POINTER(_D), _P]),
     ("nk_mems_params_default", C.c_int, [C.POINTER(nk_mems_params)]),
     ("nk_mems_create", C.c_int, [C.POINTER(_P), C.POINTER(nk_mems_params), C.POINTER(nk_opts),
                                  _P]),

@@ -74,6 +74,30 @@ def sh_precond(v, h, r, k, ny=None, nx=None, out=None):
     return out
 
 
+def shlin_precond(v, h, r, k, sigma=0.0, ny=None, nx=None, dot_with=None, out=None):
+    """``M @ v`` with M = ((1 + sigma) I - (k/2) L)^-1 on the periodic grid, the spectral
+    preconditioner of ``SHLinearised(precond="spectral")`` (at sigma = 0: ``sh_precond(v) / k``).
+    nx, ny powers of two in [8, 4096], k r < 2, sigma >= 0; ``out`` may be ``v``.  With
+    ``dot_with=w`` returns ``(z, w . z)``: the last FFT pass forms the dot itself, in a fixed
+    summation order; ``z`` is the same either way."""
+    _dev(v, "v")
+    ny, nx = _grid(v, ny, nx)
+    out = torch.empty_like(v) if out is None else _dev(out, "out")
+    if out.numel() != v.numel():
+        raise ValueError("shlin_precond: size mismatch")
+    w, dot = None, None
+    if dot_with is not None:
+        w = _dev(dot_with, "dot_with")
+        if w.numel() != v.numel():
+            raise ValueError("shlin_precond: size mismatch")
+        dot = C.c_double()
+    check(lib.nk_shlin_precond_apply(_ptr(v), _ptr(out), ny, nx, float(h), float(r), float(k),
+                                     float(sigma), _ptr(w) if w is not None else None,
+                                     C.byref(dot) if dot is not None else None, _stream()),
+          "nk_shlin_precond_apply")
+    return out if dot is None else (out, dot.value)
+
+
 def sh_residual(u, uo, h, r, k, g, ny=None, nx=None, out=None):
     """``residual(u)`` of sh_scipy_nk.py:47-49 with ``Uo = uo``, fused into one pass."""
     _dev(u, "u")
