@@ -49,6 +49,37 @@ int reduce_call(int64_t n, int nslots, int nsum, int nv, double* out, hipStream_
   return hip_rc(e);
 }
 
+// A spectral-preconditioner plan for the length of one call: built, handed to `body`, destroyed.
+// hipErrorInvalidValue is a refusal of fftpc_apply's (alignment, aliasing): the caller's NK_EINVAL.
+template <class L>
+int with_precond_plan(int64_t ny, int64_t nx, double h, double r, double k, L&& body) {
+  FftPcPlan plan;
+  if (const int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr)) return rc;
+  const hipError_t e = body(plan);
+  fftpc_destroy(&plan);
+  return e == hipErrorInvalidValue ? NK_EINVAL : hip_rc(e);
+}
+
+// z = scale (I (1 + sigma)/k - L/2)^-1 v and, with w, *dot_host = w . z; synchronises s.
+int precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r, double k,
+                  double sigma, double scale, const double* w, double* dot_host, hipStream_t s) {
+  if (!v || !z || (w == nullptr) != (dot_host == nullptr)) return NK_EINVAL;
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return NK_EINVAL;
+  return with_precond_plan(ny, nx, h, r, k, [&](const FftPcPlan& plan) {
+    double* red = nullptr;  // the block partials, then the sum
+    const int64_t nb = fftpc_dot_blocks(plan);
+    hipError_t e = hipSuccess;
+    if (w) e = hipMalloc(reinterpret_cast<void**>(&red), sizeof(double) * size_t(nb + 1));
+    if (e == hipSuccess) e = fftpc_apply(plan, v, z, (1.0 + sigma) / k, scale, w, red, nullptr, s);
+    if (e == hipSuccess && w) e = reduce_final_launch(red, nb, 1, 1, red + nb, nullptr, s);
+    if (e == hipSuccess && w)
+      e = hipMemcpyAsync(dot_host, red + nb, sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (red) hipFree(red);
+    return e;
+  });
+}
+
 }  // namespace
 
 struct nk_sh {
@@ -817,15 +848,7 @@ int64_t nk_sh_precond_applies(nk_sh* s) { return s ? s->NK->precond_applies() : 
 
 int nk_sh_precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
                         double k, void* stream) {
-  if (!v || !z) return NK_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z)) & 15u) return NK_EINVAL;
-  FftPcPlan plan;
-  int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr);
-  if (rc) return rc;
-  hipError_t e = fftpc_apply(plan, v, z, S(stream));
-  if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-  fftpc_destroy(&plan);
-  return hip_rc(e);
+  return precond_apply(v, z, ny, nx, h, r, k, 0.0, 1.0, nullptr, nullptr, S(stream));  // M itself
 }
 
 // ------------------------------------------------------------------------------ generic
@@ -1023,67 +1046,41 @@ double nk_shlin_precond_shift(nk_shlin* s) {
 int nk_shlin_precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
                            double k, double sigma, const double* w, double* dot_host,
                            void* stream) {
-  if (!v || !z || (w == nullptr) != (dot_host == nullptr)) return NK_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(z) |
-       reinterpret_cast<uintptr_t>(w)) & 15u)
-    return NK_EINVAL;
-  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return NK_EINVAL;
-  FftPcPlan plan;
-  int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr);
-  if (rc) return rc;
-  double* red = nullptr;  // the block partials, then the sum
-  const int64_t nb = fftpc_dot_blocks(plan);
-  hipError_t e = hipSuccess;
-  if (w) e = hipMalloc(reinterpret_cast<void**>(&red), sizeof(double) * size_t(nb + 1));
-  int64_t nblk = 0;
-  if (e == hipSuccess)
-    e = fftpc_apply_shift(plan, v, z, (1.0 + sigma) / k, 1.0 / k, w, red, &nblk, S(stream));
-  if (e == hipSuccess && w)
-    e = reduce_final_launch(red, nblk, 1, 1, red + nb, nullptr, S(stream));
-  if (e == hipSuccess && w)
-    e = hipMemcpyAsync(dot_host, red + nb, sizeof(double), hipMemcpyDeviceToHost, S(stream));
-  if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-  if (red) hipFree(red);
-  fftpc_destroy(&plan);
-  return hip_rc(e);
+  return precond_apply(v, z, ny, nx, h, r, k, sigma, 1.0 / k, w, dot_host, S(stream));
 }
 
 int nk_debug_shlin_precond_time(int64_t ny, int64_t nx, double h, double r, double k, double sigma,
                                 int32_t reps, double* ms_plain, double* ms_dot, void* stream) {
   if (reps < 1 || !ms_plain || !ms_dot || !(sigma >= 0.0) || !std::isfinite(sigma))
     return NK_EINVAL;
-  FftPcPlan plan;
-  int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr);
-  if (rc) return rc;
-  const size_t n = size_t(ny * nx);
-  const int64_t nb = fftpc_dot_blocks(plan);
-  double* buf = nullptr;  // v, z, then the block partials
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), sizeof(double) * (2 * n + size_t(nb)));
-  if (e == hipSuccess) e = hipMemsetAsync(buf, 0, sizeof(double) * (2 * n + size_t(nb)), S(stream));
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-  double* out[2] = {ms_plain, ms_dot};
-  for (int leg = 0; leg < 2 && e == hipSuccess; ++leg) {
-    const double* w = leg ? buf : nullptr;
-    double* part = leg ? buf + 2 * n : nullptr;
-    // one untimed application first (code object load, caches), then reps between two events
-    for (int i = 0; i <= reps && e == hipSuccess; ++i) {
-      if (i == 1) e = hipEventRecord(ev[0], S(stream));
-      if (e == hipSuccess)
-        e = fftpc_apply_shift(plan, buf, buf + n, (1.0 + sigma) / k, 1.0 / k, w, part, nullptr,
-                              S(stream));
+  return with_precond_plan(ny, nx, h, r, k, [&](const FftPcPlan& plan) {
+    const size_t n = size_t(ny * nx), len = 2 * n + size_t(fftpc_dot_blocks(plan));
+    double* buf = nullptr;  // v, z, then the block partials
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), sizeof(double) * len);
+    if (e == hipSuccess) e = hipMemsetAsync(buf, 0, sizeof(double) * len, S(stream));
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    for (int leg = 0; leg < 2 && e == hipSuccess; ++leg) {
+      const double* w = leg ? buf : nullptr;
+      double* part = leg ? buf + 2 * n : nullptr;
+      // one untimed application first (code object load, caches), then reps between two events
+      for (int i = 0; i <= reps && e == hipSuccess; ++i) {
+        if (i == 1) e = hipEventRecord(ev[0], S(stream));
+        if (e == hipSuccess)
+          e = fftpc_apply(plan, buf, buf + n, (1.0 + sigma) / k, 1.0 / k, w, part, nullptr,
+                          S(stream));
+      }
+      if (e == hipSuccess) e = hipEventRecord(ev[1], S(stream));
+      if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+      float ms = 0.0f;
+      if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+      *(leg ? ms_dot : ms_plain) = double(ms) / reps;
     }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], S(stream));
-    if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    *out[leg] = double(ms) / reps;
-  }
-  for (int i = 0; i < 2; ++i)
-    if (ev[i]) hipEventDestroy(ev[i]);
-  if (buf) hipFree(buf);
-  fftpc_destroy(&plan);
-  return hip_rc(e);
+    for (int i = 0; i < 2; ++i)
+      if (ev[i]) hipEventDestroy(ev[i]);
+    if (buf) hipFree(buf);
+    return e;
+  });
 }
 
 // ------------------------------------------------------------------------------ PMA2 (MEMS)

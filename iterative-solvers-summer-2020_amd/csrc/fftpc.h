@@ -1,9 +1,12 @@
-// Spectral preconditioner of the Swift-Hohenberg Newton-Krylov step (fftpc.hip):
-//   z = M v = IFFT2( FFT2(v) / A0^ ),  A0 = I/k - L/2 on a periodic ny x nx grid,
-// the exact inverse of the linear part of the Crank-Nicolson Jacobian (L the 13-point operator of
+// Spectral preconditioner of the two Swift-Hohenberg solvers (fftpc.hip):
+//   z = scale * IFFT2( FFT2(v) / (ik - L^/2) )  on a periodic ny x nx grid,
+// the inverse of a constant-coefficient operator ik I - L/2 (L the 13-point operator of
 // stencil.hip), diagonal in Fourier space:
-//   s(p,q) = (2 cos(2 pi p/ny) + 2 cos(2 pi q/nx) - 4)/h^2,  L^ = -s^2 - 2 s + (r - 1),
-//   A0^ = 1/k - L^/2.
+//   s(p,q) = (2 cos(2 pi p/ny) + 2 cos(2 pi q/nx) - 4)/h^2,  L^ = -s^2 - 2 s + (r - 1).
+// The Newton-Krylov step (sh_problem.cpp) uses M = A0^-1, A0 = I/k - L/2 the linear part of the
+// Crank-Nicolson Jacobian: ik = 1/k, scale = 1.  The semi-implicit stepper's CG solve (shlin.cpp)
+// uses ((1 + sigma) I - L k/2)^-1 with a shift sigma chosen every step: ik = (1 + sigma)/k,
+// scale = 1/k, and the dot r . z from the last pass.
 // No FFT library: three hand-written passes (rows real-to-complex, columns forward + symbol +
 // inverse on chip, rows complex-to-real), 48 B per grid point.
 #pragma once
@@ -34,19 +37,23 @@ int fftpc_check(int64_t ny, int64_t nx, double h, double r, double k);
 // and owns it).
 int fftpc_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, double k, double* work);
 void fftpc_destroy(FftPcPlan* p);
-// out = M in (three launches on s; in == out allowed; no synchronisation, no allocation).
-hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStream_t s);
-// The same passes with the symbol's constants given per application: out = scale * (ik I - L/2)^-1
-// in (fftpc_apply is ik = 1/k, scale = 1, in the plan's own arithmetic).  A shifted operator
-// ((1 + sigma) I - (k/2) L)^-1 is ik = (1 + sigma)/k, scale = 1/k; ik > (r - 1)/2 keeps the symbol
-// positive.  The tables do not depend on ik: no plan rebuild, no allocation, no synchronisation.
-// With w (16-B aligned; may be `in` or `out`), the last pass also multiplies every value it stores
-// by the matching entry of w and leaves one partial sum per block in partial[0, *nblk)
+// out = scale * (ik I - L/2)^-1 in, the symbol's constants given per application (three launches
+// on s; in == out allowed).  A shifted operator ((1 + sigma) I - (k/2) L)^-1 is
+// ik = (1 + sigma)/k, scale = 1/k.  The tables do not depend on ik: no plan rebuild, no
+// allocation, no synchronisation.
+// With w (may be `in` or `out`), the last pass also multiplies every value it stores by the
+// matching entry of w and leaves one partial sum per block in partial[0, *nblk)
 // (fftpc_dot_blocks(p) <= 4096 values); summed in order (reduce_final_launch) they give w . out,
-// bit-reproducibly.  w and partial are given together or not at all.
-hipError_t fftpc_apply_shift(const FftPcPlan& p, const double* in, double* out, double ik,
-                             double scale, const double* w, double* partial, int64_t* nblk,
-                             hipStream_t s);
+// bit-reproducibly.
+// hipErrorInvalidValue, and nothing launched, unless: the plan is built; in, out and w are 16-B
+// aligned and none of them is the plan's work buffer; w and partial are given together or not at
+// all; ik and scale are finite and ik > (r - 1)/2 (the symbol stays positive).
+hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, double ik, double scale,
+                       const double* w, double* partial, int64_t* nblk, hipStream_t s);
+// out = M in: the plan's own ik = 1/k, scale = 1, no dot.
+inline hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStream_t s) {
+  return fftpc_apply(p, in, out, p.ik, 1.0, nullptr, nullptr, nullptr, s);
+}
 // blocks of a row pass = partial sums of an application with the dot
 inline int64_t fftpc_dot_blocks(const FftPcPlan& p) { return p.rows > 0 ? p.ny / p.rows : 0; }
 // algorithmic HBM bytes of one application (fftpc_dot_bytes: the last pass also reads w)

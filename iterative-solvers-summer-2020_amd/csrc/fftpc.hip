@@ -184,14 +184,11 @@ __global__ __launch_bounds__(kRowThreads) void fftpc_rows_fwd(const double* __re
 
 // Pass 3: the inverse of pass 1 (factors of 2 left to the symbol's normalisation): Z[k] = E + i O
 // with E = X[k] + conj X[n2-k], O = conj(w^k) (X[k] - conj X[n2-k]); the backward transform of Z
-// is nx (x[2j] + i x[2j+1]).
-__global__ __launch_bounds__(kRowThreads) void fftpc_rows_inv(const cd* __restrict__ H,
-                                                              double* __restrict__ out, int nx,
-                                                              int lx2, int rows,
-                                                              const cd* __restrict__ twx) {
+// is nx (x[2j] + i x[2j+1]).  The block's rows are left in fft_lds, row-major, behind a barrier;
+// the two kernels below differ only in how they store them.
+__device__ __forceinline__ void rows_inv_lds(const cd* __restrict__ H, int n2, int lx2, int rows,
+                                             int64_t row0, const cd* __restrict__ twx) {
   cd* buf = fft_lds;
-  const int n2 = nx >> 1;
-  const int64_t row0 = int64_t(blockIdx.x) * rows;
   const int per = (n2 >> 1) + 1;
   for (int idx = threadIdx.x; idx < rows * per; idx += blockDim.x) {
     const int b = idx / per, k = idx - b * per;
@@ -211,6 +208,16 @@ __global__ __launch_bounds__(kRowThreads) void fftpc_rows_inv(const cd* __restri
   }
   __syncthreads();
   fft_inv(buf, lx2, rows, twx, 2);
+}
+
+__global__ __launch_bounds__(kRowThreads) void fftpc_rows_inv(const cd* __restrict__ H,
+                                                              double* __restrict__ out, int nx,
+                                                              int lx2, int rows,
+                                                              const cd* __restrict__ twx) {
+  const cd* buf = fft_lds;
+  const int n2 = nx >> 1;
+  const int64_t row0 = int64_t(blockIdx.x) * rows;
+  rows_inv_lds(H, n2, lx2, rows, row0, twx);
   cd* dst = reinterpret_cast<cd*>(out) + row0 * n2;
   const int total = rows * n2;
   for (int idx = threadIdx.x; idx < total; idx += blockDim.x) dst[idx] = buf[idx];
@@ -228,28 +235,10 @@ __global__ __launch_bounds__(kRowThreads) void fftpc_rows_inv_dot(const cd* __re
                                                                   const cd* __restrict__ twx,
                                                                   const double* w,
                                                                   double* __restrict__ partial) {
-  cd* buf = fft_lds;
+  const cd* buf = fft_lds;
   const int n2 = nx >> 1;
   const int64_t row0 = int64_t(blockIdx.x) * rows;
-  const int per = (n2 >> 1) + 1;
-  for (int idx = threadIdx.x; idx < rows * per; idx += blockDim.x) {
-    const int b = idx / per, k = idx - b * per;
-    cd* z = buf + (b << lx2);
-    const cd* src = H + (row0 + b) * n2;
-    if (k == 0) {
-      const cd x0 = src[0];
-      z[0] = cd{x0.x + x0.y, x0.x - x0.y};
-      continue;
-    }
-    const int m = n2 - k;
-    const cd xk = src[k], xm = src[m];
-    const cd E = cd{xk.x + xm.x, xk.y - xm.y};
-    const cd O = cmulc(cd{xk.x - xm.x, xk.y + xm.y}, twx[k]);
-    z[brev(k, lx2)] = cd{E.x - O.y, E.y + O.x};
-    if (m != k) z[brev(m, lx2)] = cd{E.x + O.y, O.x - E.y};
-  }
-  __syncthreads();
-  fft_inv(buf, lx2, rows, twx, 2);
+  rows_inv_lds(H, n2, lx2, rows, row0, twx);
   cd* dst = reinterpret_cast<cd*>(out) + row0 * n2;
   const cd* wv = reinterpret_cast<const cd*>(w) + row0 * n2;
   const int total = rows * n2;
@@ -417,16 +406,19 @@ void fftpc_destroy(FftPcPlan* p) {
   *p = FftPcPlan{};
 }
 
-namespace {
-// The three passes with the symbol's constants given: out = IFFT2(FFT2(in) * scale / (ik - L^/2))
-// (scale includes the transforms' 1/(nx ny)); with w, the last pass also leaves the block
-// partials of w . out.
-hipError_t apply_passes(const FftPcPlan& p, const double* in, double* out, double ik, double scale,
-                        const double* w, double* partial, hipStream_t s) {
-  if (!p.tables || !p.work || !in || !out || in == p.work || out == p.work)
+// The three passes: out = IFFT2(FFT2(in) * scale / (ik - L^/2)), the transforms' 1/(nx ny) folded
+// into the symbol; with w, the last pass also leaves the block partials of w . out.
+hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, double ik, double scale,
+                       const double* w, double* partial, int64_t* nblk, hipStream_t s) {
+  if (!p.tables || !p.work || !in || !out || in == p.work || out == p.work || w == p.work)
     return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u)
+  if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) |
+       reinterpret_cast<uintptr_t>(w)) & 15u)
     return hipErrorInvalidValue;
+  if ((w == nullptr) != (partial == nullptr)) return hipErrorInvalidValue;
+  if (!(ik > 0.5 * (p.r - 1.0)) || !std::isfinite(ik) || !std::isfinite(scale))
+    return hipErrorInvalidValue;  // the symbol ik - L^/2 >= ik - (r - 1)/2 must stay positive
+  if (nblk) *nblk = fftpc_dot_blocks(p);
   const int nx = int(p.nx), ny = int(p.ny), n2 = nx / 2;
   const cd* twx = reinterpret_cast<const cd*>(p.tables);
   const cd* twy = reinterpret_cast<const cd*>(p.tables + p.nx);
@@ -434,7 +426,7 @@ hipError_t apply_passes(const FftPcPlan& p, const double* in, double* out, doubl
   const size_t row_lds = sizeof(cd) * size_t(p.rows) * size_t(n2);
   const size_t col_lds = sizeof(cd) * size_t(ny) * size_t(p.cols);
   const int col_threads = std::min(kColThreadsMax, std::max(64, (ny * p.cols) / 4));
-  Symbol sym{p.ih2, p.r, ik, scale};
+  Symbol sym{p.ih2, p.r, ik, scale / (double(p.nx) * double(p.ny))};
   fftpc_rows_fwd<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(in, H, nx, p.lx2, p.rows,
                                                                       twx);
   fftpc_cols<<<dim3(n2 / p.cols), dim3(col_threads), col_lds, s>>>(H, ny, n2, p.ly,
@@ -446,22 +438,6 @@ hipError_t apply_passes(const FftPcPlan& p, const double* in, double* out, doubl
     fftpc_rows_inv<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(H, out, nx, p.lx2,
                                                                         p.rows, twx);
   return hipGetLastError();
-}
-}  // namespace
-
-hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, hipStream_t s) {
-  return apply_passes(p, in, out, p.ik, 1.0 / (double(p.nx) * double(p.ny)), nullptr, nullptr, s);
-}
-
-hipError_t fftpc_apply_shift(const FftPcPlan& p, const double* in, double* out, double ik,
-                             double scale, const double* w, double* partial, int64_t* nblk,
-                             hipStream_t s) {
-  if (!(ik > 0.5 * (p.r - 1.0)) || !std::isfinite(ik) || !std::isfinite(scale))
-    return hipErrorInvalidValue;  // the symbol ik - L^/2 >= ik - (r - 1)/2 must stay positive
-  if ((w == nullptr) != (partial == nullptr) || (w && w == p.work)) return hipErrorInvalidValue;
-  if (reinterpret_cast<uintptr_t>(w) & 15u) return hipErrorInvalidValue;
-  if (nblk) *nblk = fftpc_dot_blocks(p);
-  return apply_passes(p, in, out, ik, scale / (double(p.nx) * double(p.ny)), w, partial, s);
 }
 
 }  // namespace nk

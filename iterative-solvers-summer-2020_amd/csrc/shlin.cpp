@@ -66,99 +66,48 @@ int ShLinStepper::set_precond(int kind) {
 int ShLinStepper::precond(const double* r, double* z, double sigma, int64_t* nblk) {
   // ((1 + sigma) I - L k/2)^-1 = (1/k) (I (1 + sigma)/k - L/2)^-1
   return E.launch(K_PRECOND, fftpc_dot_bytes(ny_, nx_), [&] {
-    return fftpc_apply_shift(pc_, r, z, (1.0 + sigma) / k_, 1.0 / k_, r, E.partial(), nblk, E.s);
+    return fftpc_apply(pc_, r, z, (1.0 + sigma) / k_, 1.0 / k_, r, E.partial(), nblk, E.s);
   });
 }
 
-// The step with M: as step() below, with z = M r in the place of r in the search direction and
-// rho = r.z in the place of r.r in alpha and beta; the stop still tests r.r.
-int ShLinStepper::step_pcg(const double* U, const double* Uo, double* Unew, ShLinStats* st) {
+// One CG body for both solves.  With M, z = M r stands in the place of r in the search direction
+// and rho = r.z in the place of r.r in alpha and beta; the stop still tests r.r.  Without M, z is r
+// and rho is r.r: the launches and read-backs are those of plain CG, and z_ is not touched.
+int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinStats* st) {
+  if (status_) return status_;
+  last_ = ShLinStats{};
   const int64_t n = E.n;
   double *x = v_[0], *r = v_[1], *p = v_[2], *pn = v_[3], *q = v_[4], *d = v_[5], *zero = v_[6],
-         *b = v_[7], *z = z_;
+         *b = v_[7], *z = pc_on_ ? z_ : r;
   constexpr int kSlotAux = Engine::kSlotCombo;  // a result read together with the next reduce()
   int64_t nblk = 0, napp = 0;
-  double red[3];
-  last_ = ShLinStats{};
-  int rc = E.launch(K_AXPBY, 24.0 * n, [&] {
-    return shlin_diag_sum_launch(U, Uo, k_, g_, d, n, E.partial(), E.s, &nblk);
-  });
-  if (!rc) rc = E.reduce_async(nblk, 1, 1, kSlotAux);  // sum D, read after the next reduce()
-  if (!rc) rc = linop(U, U, 0.0, zero, -k_ / 2, pn, b, &nblk);
-  VecList none{};
-  if (!rc) rc = E.launch(K_COMBO, 16.0 * n, [&] {
-    return combo_launch(b, b, 1.0, none, 0, n, E.partial(), E.s, &nblk);
-  });
-  if (!rc) rc = E.reduce(nblk, 1, 2, red);
-  if (rc) return rc;
-  const double bnorm = std::sqrt(red[0]);
-  const double dmean = *E.hres(kSlotAux) / double(n);
-  if (!std::isfinite(dmean)) return NK_NONFINITE;
-  const double sigma = dmean > 0.0 ? dmean : 0.0;
-  last_.shift = sigma;
-  if (st) *st = last_;
-  // warm start x = U: r = b - A U, z = M r
-  rc = E.copy(x, U, n);
-  if (!rc) rc = linop(U, U, 0.0, d, k_ / 2, pn, q, &nblk);
-  VecList mq{};
-  mq.p[0] = q;
-  mq.c[0] = -1.0;
-  if (!rc) rc = E.launch(K_COMBO, 24.0 * n, [&] {
-    return combo_launch(r, b, 1.0, mq, 1, n, E.partial(), E.s, &nblk);
-  });
-  if (!rc) rc = E.reduce_async(nblk, 1, 1, kSlotAux);
-  if (!rc) rc = precond(r, z, sigma, &nblk);
-  ++napp;
-  if (!rc) rc = E.reduce(nblk, 1, 1, red);
-  if (rc) return rc;
-  double rr = *E.hres(kSlotAux), rho = red[0];
-  const double stop = rtol_ * bnorm;
-  double beta = 0.0;
-  int64_t it = 0;
-  while (std::sqrt(rr) > stop && it < maxiter_) {
-    if (!(rho > 0.0)) return NK_NONFINITE;  // M is positive definite: non-finite data
-    // p' = z + beta p; q = A p'; p'.q
-    rc = linop(z, it == 0 ? z : p, beta, d, k_ / 2, pn, q, &nblk);
-    if (!rc) rc = E.reduce(nblk, 1, 3, red);
-    if (rc) return rc;
-    const double pq = red[0];
-    if (!(pq > 0.0)) return NK_NONFINITE;  // not SPD (g k U dominated) or non-finite data
-    const double alpha = rho / pq;
-    rc = E.launch(K_AXPBY, 48.0 * n, [&] {
-      return cg_update_launch(x, r, pn, q, alpha, n, E.partial(), E.s, &nblk);
-    });
-    if (!rc) rc = E.reduce_async(nblk, 1, 1, kSlotAux);
-    // queued behind the update: r.r and r.z come back together
+  double red[3], sigma = 0.0, rr = 0.0, rho = 0.0;
+  // rr = r.r and rho = r.z after a pass that wrote r and left nv values per block, r.r first.
+  auto residual_dots = [&](int nv) {
+    if (!pc_on_) {
+      const int rc = E.reduce(nblk, 1, nv, red);
+      if (!rc) rr = rho = red[0];
+      return rc;
+    }
+    // M queued behind the pass before r.r is known: r.r and r.z come back together
+    int rc = E.reduce_async(nblk, 1, 1, kSlotAux);
     if (!rc) rc = precond(r, z, sigma, &nblk);
     ++napp;
     if (!rc) rc = E.reduce(nblk, 1, 1, red);
     if (rc) return rc;
     rr = *E.hres(kSlotAux);
-    beta = red[0] / rho;
     rho = red[0];
-    std::swap(p, pn);
-    ++it;
+    return rc;
+  };
+  int rc;
+  if (pc_on_) {
+    rc = E.launch(K_AXPBY, 24.0 * n, [&] {
+      return shlin_diag_sum_launch(U, Uo, k_, g_, d, n, E.partial(), E.s, &nblk);
+    });
+    if (!rc) rc = E.reduce_async(nblk, 1, 1, kSlotAux);  // sum D, read after the next reduce()
+  } else {
+    rc = E.launch(K_AXPBY, 24.0 * n, [&] { return shlin_diag_launch(U, Uo, k_, g_, d, n, E.s); });
   }
-  rc = E.copy(Unew, x, n);
-  if (!rc) rc = E.sync();
-  last_.iters = it;
-  last_.relres = bnorm > 0 ? std::sqrt(rr) / bnorm : std::sqrt(rr);
-  last_.precond_applies = napp;
-  if (st) *st = last_;
-  if (rc) return rc;
-  return std::isfinite(rr) ? (std::sqrt(rr) <= stop ? NK_OK : NK_NO_CONVERGENCE) : NK_NONFINITE;
-}
-
-int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinStats* st) {
-  if (status_) return status_;
-  if (pc_on_) return step_pcg(U, Uo, Unew, st);
-  last_ = ShLinStats{};
-  const int64_t n = E.n;
-  double *x = v_[0], *r = v_[1], *p = v_[2], *pn = v_[3], *q = v_[4], *d = v_[5], *zero = v_[6],
-         *b = v_[7];
-  int64_t nblk = 0;
-  double red[3];
-  int rc = E.launch(K_AXPBY, 24.0 * n, [&] { return shlin_diag_launch(U, Uo, k_, g_, d, n, E.s); });
   // b = (I + L k/2) U  (the zero vector stands in for D)
   if (!rc) rc = linop(U, U, 0.0, zero, -k_ / 2, pn, b, &nblk);
   // |b|^2 (combo rewrites b unchanged and sums its squares)
@@ -169,8 +118,15 @@ int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinSta
   if (!rc) rc = E.reduce(nblk, 1, 2, red);
   if (rc) return rc;
   const double bnorm = std::sqrt(red[0]);
-  // warm start x = U: r = b - A U
-  if (!rc) rc = E.copy(x, U, n);
+  if (pc_on_) {
+    const double dmean = *E.hres(kSlotAux) / double(n);
+    if (!std::isfinite(dmean)) return NK_NONFINITE;
+    sigma = dmean > 0.0 ? dmean : 0.0;
+    last_.shift = sigma;
+    if (st) *st = last_;
+  }
+  // warm start x = U: r = b - A U (and z = M r)
+  rc = E.copy(x, U, n);
   if (!rc) rc = linop(U, U, 0.0, d, k_ / 2, pn, q, &nblk);
   VecList mq{};
   mq.p[0] = q;
@@ -178,27 +134,27 @@ int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinSta
   if (!rc) rc = E.launch(K_COMBO, 24.0 * n, [&] {
     return combo_launch(r, b, 1.0, mq, 1, n, E.partial(), E.s, &nblk);
   });
-  if (!rc) rc = E.reduce(nblk, 1, 2, red);
+  if (!rc) rc = residual_dots(2);
   if (rc) return rc;
-  double rr = red[0];
   const double stop = rtol_ * bnorm;
   double beta = 0.0;
   int64_t it = 0;
   while (std::sqrt(rr) > stop && it < maxiter_) {
-    // p' = r + beta p; q = A p'; p'.q
-    rc = linop(r, it == 0 ? r : p, beta, d, k_ / 2, pn, q, &nblk);
+    // M is positive definite: non-finite data (without M, rho = r.r > stop^2 here)
+    if (!(rho > 0.0)) return NK_NONFINITE;
+    // p' = z + beta p; q = A p'; p'.q
+    rc = linop(z, it == 0 ? z : p, beta, d, k_ / 2, pn, q, &nblk);
     if (!rc) rc = E.reduce(nblk, 1, 3, red);
     if (rc) return rc;
     const double pq = red[0];
     if (!(pq > 0.0)) return NK_NONFINITE;  // not SPD (g k U dominated) or non-finite data
-    const double alpha = rr / pq;
+    const double alpha = rho / pq, rho_old = rho;
     rc = E.launch(K_AXPBY, 48.0 * n, [&] {
       return cg_update_launch(x, r, pn, q, alpha, n, E.partial(), E.s, &nblk);
     });
-    if (!rc) rc = E.reduce(nblk, 1, 1, red);
+    if (!rc) rc = residual_dots(1);
     if (rc) return rc;
-    beta = red[0] / rr;
-    rr = red[0];
+    beta = rho / rho_old;
     std::swap(p, pn);
     ++it;
   }
@@ -206,6 +162,7 @@ int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinSta
   if (!rc) rc = E.sync();
   last_.iters = it;
   last_.relres = bnorm > 0 ? std::sqrt(rr) / bnorm : std::sqrt(rr);
+  last_.precond_applies = napp;
   if (st) *st = last_;
   if (rc) return rc;
   return std::isfinite(rr) ? (std::sqrt(rr) <= stop ? NK_OK : NK_NO_CONVERGENCE) : NK_NONFINITE;

@@ -50,7 +50,6 @@ class ShLinStepper {
             double* w, double* out, int64_t* nblk);
   // z = M r and the block partials of r . z (*nblk of them)
   int precond(const double* r, double* z, double sigma, int64_t* nblk);
-  int step_pcg(const double* U, const double* Uo, double* Unew, ShLinStats* st);
   int64_t ny_, nx_;
   double h_, r_;
   double g_, k_, rtol_;

@@ -121,6 +121,24 @@ def test_shift(name):
         s.close()
 
 
+def test_shift_reported_without_convergence():
+    """A step that ends in NoConvergence still reports its sigma and its applications of M."""
+    import nkhip
+    U, Uo, ny, nx, h, g = sp.state("stiff64")
+    s = nkhip.SHLinearised(N=nx, ny=ny, d=nx * h, k=sp.K, r=sp.R, g=g, precond="spectral",
+                           maxiter=2)
+    try:
+        with pytest.raises(nkhip.NoConvergence):
+            s.step(U, Uo)
+        want = float(sp.shift(U, Uo, sp.K, g, dtype=LD))
+        print(f"stiff64, maxiter 2: last_shift {s.last_shift!r}, longdouble {want!r}, "
+              f"iterations {s.last_iters}, M applications {s.last_precond}")
+        assert want > 0.0 and abs(s.last_shift - want) <= 1e-14 * want
+        assert s.last_iters == 2 and s.last_precond == 3  # the start's and one per iteration
+    finally:
+        s.close()
+
+
 # ------------------------------------------------------------------------ 4. reference parity
 def test_golden_steps_with_preconditioner():
     import nkhip
