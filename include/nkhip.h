@@ -166,8 +166,9 @@ int64_t nk_arnoldi_mbox_launches(void);
  * L^ = -s^2 - 2 s + (r-1), s = (2 cos(2 pi p/ny) + 2 cos(2 pi q/nx) - 4)/h^2.  The operator of
  * NK_PC_SPECTRAL alone, as nk_sh13_apply is for L; replaces an `inner_M` a caller of
  * scipy.optimize.newton_krylov (scipy/optimize/_nonlin.py:1463-1467) would build with
- * scipy.fft.  Hand-written transforms, no FFT library.  nx, ny powers of two in [8, 4096] (they may
- * differ), k > 0, k r < 2 (A0^ > 0), 16-B aligned vectors, z == v allowed; NK_EINVAL otherwise.
+ * scipy.fft.  Hand-written transforms, no FFT library.  nx, ny powers of two in [8, 16384] (they
+ * may differ; columns longer than 4096 are transformed in two factors, see NKHIP_FFTPC_SPLIT in
+ * DESIGN.md), k > 0, k r < 2 (A0^ > 0), 16-B aligned vectors, z == v allowed; NK_EINVAL otherwise.
  * Builds its tables and workspace per call and synchronises `stream` (a stepper keeps them). */
 int nk_sh_precond_apply(const double* v_dev, double* z_dev, int64_t ny, int64_t nx, double h,
                         double r, double k, void* stream);
@@ -344,7 +345,7 @@ int64_t nk_sh_workspace_bytes(nk_sh* s);
  * 166-177, _gcrotmk.py:112-121).  As there: the outer residual and the tolerance stay
  * unpreconditioned, v0 = M F, and every Arnoldi vector is M (J z).  NK_PC_NONE restores the
  * unpreconditioned solver exactly.  NK_PC_SPECTRAL (see nk_sh_precond_apply) needs a single slab
- * (comm == NULL), nx and ny powers of two in [8, 4096] and k r < 2; NK_EINVAL otherwise, and the
+ * (comm == NULL), nx and ny powers of two in [8, 16384] and k r < 2; NK_EINVAL otherwise, and the
  * stepper stays as it was.  The first NK_PC_SPECTRAL builds the tables and takes two vectors of
  * workspace (counted by nk_sh_workspace_bytes); no step allocates.  A preconditioned step runs
  * the host loop: one JVP pass and one application of M per Arnoldi step, no fused step. */
@@ -441,7 +442,7 @@ int nk_shlin_step(nk_shlin* s, const double* U_dev, const double* Uo_dev, double
  * exactly.  NK_PC_SPECTRAL: preconditioned CG with the constant-coefficient part of the matrix,
  *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean(D), 0)  (recomputed every step),
  * applied in Fourier space by the passes of nk_sh_precond_apply; the stopping rule is unchanged
- * (the recursive unpreconditioned residual).  Needs nx and ny powers of two in [8, 4096] and
+ * (the recursive unpreconditioned residual).  Needs nx and ny powers of two in [8, 16384] and
  * k r < 2; NK_EINVAL otherwise, and the stepper stays as it was.  The first NK_PC_SPECTRAL builds
  * the tables and takes two vectors of workspace; no step allocates. */
 int nk_shlin_set_precond(nk_shlin* s, int32_t kind);

@@ -28,10 +28,19 @@
 // columns, which lets the other half of a 128-B line come from that L2.  Transposed tiles out of
 // the row pass would make these runs long, at the cost of short runs in the row passes'
 // stores (a row of 4096 is already 32 KB of LDS per row).
+//
+// Sides of 8192 and 16384 take other kernels, and every grid with both sides <= 4096 launches the
+// three above exactly as before.  A column longer than 4096 (256 KB at 16384) does not fit on
+// chip: pass 2 becomes three trips over the half spectrum, the column length in two factors
+// (fftpc_cols_outer / fftpc_cols_inner below, 80 B per point in all).  A row longer than 4096 is
+// 64 or 128 KB of LDS: one row per block of 1024 threads (fftpc_rows_*_long), whose blocks take
+// several rows in turn where there are more than 4096, so that a row pass never leaves more than
+// 4096 dot partials.
 #include "fftpc.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "../../include/nkhip.h"
@@ -45,6 +54,7 @@ using cd = double2;
 
 constexpr int kRowThreads = 256;
 constexpr int kColThreadsMax = 1024;
+constexpr int kLongThreads = 1024;  // block of the row passes that take several row groups in turn
 constexpr int kRowElems = 2048;  // complex values of LDS per block of a row pass (32 KB)
 
 __device__ __forceinline__ cd cadd(cd a, cd b) { return cd{a.x + b.x, a.y + b.y}; }
@@ -147,13 +157,10 @@ extern __shared__ double2 fft_lds[];
 // (length n2 = nx/2), and X[k] = E[k] + w^k O[k] (w = exp(-2 pi i/nx), E / O the transforms of the
 // even / odd samples, E[k] = (Z[k] + conj Z[n2-k])/2, O[k] = (Z[k] - conj Z[n2-k])/(2i)) written
 // for k = 0..n2 in the packed layout.
-__global__ __launch_bounds__(kRowThreads) void fftpc_rows_fwd(const double* __restrict__ in,
-                                                              cd* __restrict__ H, int nx, int lx2,
-                                                              int rows,
-                                                              const cd* __restrict__ twx) {
+__device__ __forceinline__ void rows_fwd_body(const double* __restrict__ in, cd* __restrict__ H,
+                                              int n2, int lx2, int rows, int64_t row0,
+                                              const cd* __restrict__ twx) {
   cd* buf = fft_lds;
-  const int n2 = nx >> 1;
-  const int64_t row0 = int64_t(blockIdx.x) * rows;
   const cd* src = reinterpret_cast<const cd*>(in) + row0 * n2;
   const int total = rows * n2;
   for (int idx = threadIdx.x; idx < total; idx += blockDim.x) buf[idx] = src[idx];
@@ -179,6 +186,27 @@ __global__ __launch_bounds__(kRowThreads) void fftpc_rows_fwd(const double* __re
       const cd c = csub(E, wO);
       dst[m] = cd{c.x, -c.y};
     }
+  }
+}
+
+__global__ __launch_bounds__(kRowThreads) void fftpc_rows_fwd(const double* __restrict__ in,
+                                                              cd* __restrict__ H, int nx, int lx2,
+                                                              int rows,
+                                                              const cd* __restrict__ twx) {
+  rows_fwd_body(in, H, nx >> 1, lx2, rows, int64_t(blockIdx.x) * rows, twx);
+}
+
+// Pass 1 for the grids the kernel above does not serve: rows longer than 4096 (one row of nx/2 =
+// 4096 or 8192 complex values is 64 or 128 KB of LDS, held by a block of 1024 threads), and
+// grids with more than 4096 row groups.  A block takes `iters` consecutive groups of `rows` rows
+// in turn, so a row pass never has more than 4096 blocks (fftpc_dot_blocks).
+__global__ __launch_bounds__(kLongThreads) void fftpc_rows_fwd_long(const double* __restrict__ in,
+                                                                    cd* __restrict__ H, int nx,
+                                                                    int lx2, int rows, int iters,
+                                                                    const cd* __restrict__ twx) {
+  for (int it = 0; it < iters; ++it) {
+    rows_fwd_body(in, H, nx >> 1, lx2, rows, (int64_t(blockIdx.x) * iters + it) * rows, twx);
+    __syncthreads();  // the next group's loads overwrite the rows just stored from
   }
 }
 
@@ -252,6 +280,41 @@ __global__ __launch_bounds__(kRowThreads) void fftpc_rows_inv_dot(const cd* __re
   if (threadIdx.x == 0) partial[blockIdx.x] = v;
 }
 
+// Pass 3 for the grids of fftpc_rows_fwd_long, with the dot (Dot) or without it.  A thread adds
+// its products in store order across the block's row groups, so the block's partial, and with it
+// the dot, stays a fixed-order sum.
+template <bool Dot>
+__global__ __launch_bounds__(kLongThreads) void fftpc_rows_inv_long(const cd* __restrict__ H,
+                                                                    double* out, int nx, int lx2,
+                                                                    int rows, int iters,
+                                                                    const cd* __restrict__ twx,
+                                                                    const double* w,
+                                                                    double* __restrict__ partial) {
+  const cd* buf = fft_lds;
+  const int n2 = nx >> 1;
+  const int total = rows * n2;
+  double acc[1] = {0.0};
+  for (int it = 0; it < iters; ++it) {
+    const int64_t row0 = (int64_t(blockIdx.x) * iters + it) * rows;
+    rows_inv_lds(H, n2, lx2, rows, row0, twx);
+    cd* dst = reinterpret_cast<cd*>(out) + row0 * n2;
+    const cd* wv = reinterpret_cast<const cd*>(w) + row0 * n2;
+    for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+      const cd zv = buf[idx];
+      if (Dot) {
+        const cd ww = wv[idx];
+        acc[0] += ww.x * zv.x + ww.y * zv.y;
+      }
+      dst[idx] = zv;
+    }
+    __syncthreads();  // the next group's loads overwrite the rows just stored from
+  }
+  if (Dot) {
+    const double v = block_reduce<1, 1, kLongThreads>(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = v;
+  }
+}
+
 struct Symbol {
   double ih2, r, ik, scale;
   // scale / A0^ from the two cosines
@@ -318,6 +381,132 @@ __global__ __launch_bounds__(kColThreadsMax) void fftpc_cols(cd* __restrict__ H,
   }
 }
 
+// ---- Columns too long for one block's LDS (ny > the plan's split length; 8192 and 16384 always).
+// The four-step form with ny = f1 * f2, row j = j1 f2 + j2, wavenumber p = k1 + f1 k2:
+//   Y[p] = sum_j2 W_f2^(j2 k2) [ W_ny^(k1 j2) sum_j1 W_f1^(j1 k1) x[j1 f2 + j2] ]
+// in three trips over the half spectrum, all in place:
+//   A. fftpc_cols_outer<false>: per j2, the f1-long transform of the stride-f2 sub-column, times
+//      the inter-factor twiddle W_ny^(k1 j2).  fft_fwd leaves k1 at position brev(k1) of the
+//      sub-column, i.e. in row brev(k1) f2 + j2: no reordering pass here either.
+//   B. fftpc_cols_inner: per k1, the f2-long transform of the f2 consecutive rows brev(k1) f2 + j2,
+//      the symbol at p = k1 + f1 k2, and the transform back.
+//   C. fftpc_cols_outer<true>: A backwards (conjugate twiddle, then the f1-long inverse).
+// 80 B per grid point with the two row passes instead of 48.  A tile holds only f1 (A, C) or
+// 2 f2 (B) values per column, so it is wide: 64 KB of LDS is 32 columns = 512-B runs of the half
+// spectrum at f1 = 128, and 16 columns = 256-B runs at f2 = 128 in B.
+// The length-f1 and length-f2 twiddles are strided reads of twy (strides f2 and f1), the
+// inter-factor twiddle is twy[m] or -twy[m - ny/2].
+
+// blocks that share an L2 (blockIdx % 8) take neighbouring tiles, as in fftpc_cols
+__device__ __forceinline__ int l2_block_order() {
+  int blk = blockIdx.x;
+  const int nblk = gridDim.x;
+  if ((nblk & 7) == 0) blk = (blk & 7) * (nblk >> 3) + (blk >> 3);
+  return blk;
+}
+
+// Trips A (Inv = false) and C (Inv = true): block (j2, column tile of 2^lw), hw = nx/2 columns.
+template <bool Inv>
+__global__ __launch_bounds__(kColThreadsMax) void fftpc_cols_outer(cd* __restrict__ H, int hw,
+                                                                    int l1, int l2, int lw,
+                                                                    const cd* __restrict__ twy) {
+  cd* buf = fft_lds;
+  const int f1 = 1 << l1, f2 = 1 << l2, W = 1 << lw;
+  const int hy = (f1 >> 1) << l2;  // ny / 2
+  const int blk = l2_block_order();
+  const int ntile = hw >> lw;
+  const int tile = blk & (ntile - 1), j2 = blk / ntile;
+  cd* base = H + int64_t(j2) * hw + (tile << lw);
+  const int64_t rs = int64_t(f2) * hw;  // from one row of the sub-column to the next
+  const int total = f1 << lw;
+  // exp(-2 pi i k1 j2 / ny), k1 j2 < ny
+  auto twid = [&](int m) -> cd {
+    if (m < hy) return twy[m];
+    const cd t = twy[m - hy];
+    return cd{-t.x, -t.y};
+  };
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int r = idx >> lw, c = idx & (W - 1);
+    const cd v = base[r * rs + c];
+    buf[(c << l1) + r] = Inv ? cmulc(v, twid(brev(r, l1) * j2)) : v;
+  }
+  __syncthreads();
+  if (Inv)
+    fft_inv(buf, l1, W, twy, f2);
+  else
+    fft_fwd(buf, l1, W, twy, f2);
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int r = idx >> lw, c = idx & (W - 1);
+    const cd v = buf[(c << l1) + r];
+    base[r * rs + c] = Inv ? v : cmul(v, twid(brev(r, l1) * j2));
+  }
+}
+
+// Trip B: block (pair of k1 groups, column tile of 2^lw).  Wavenumber p = k1 + f1 k2 has its
+// Hermitian partner ny - p in group f1 - k1 (mod f1), which column 0's unpacking needs beside it:
+// a block holds the two groups {k1, f1 - k1}, or {0, f1/2}, which are their own partners.
+__global__ __launch_bounds__(kColThreadsMax) void fftpc_cols_inner(cd* __restrict__ H, int hw,
+                                                                    int l1, int l2, int lw,
+                                                                    const cd* __restrict__ twy,
+                                                                    const cd* __restrict__ twx,
+                                                                    Symbol sym) {
+  cd* buf = fft_lds;
+  const int f1 = 1 << l1, f2 = 1 << l2, W = 1 << lw;
+  const int ny = f1 << l2, hy = ny >> 1;
+  const int blk = l2_block_order();
+  const int ntile = hw >> lw;
+  const int tile = blk & (ntile - 1), pr = blk / ntile;  // pr < f1/2
+  const int c0 = tile << lw;
+  const int ka = pr, kb = pr ? f1 - pr : f1 >> 1;
+  const int64_t rowa = int64_t(brev(ka, l1)) << l2, rowb = int64_t(brev(kb, l1)) << l2;
+  const int total = f2 << (lw + 1);
+  // buf[(((g << lw) + c) << l2) + j2]: group g, column c of the tile, row j2 of the group
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int c = idx & (W - 1), t = idx >> lw;
+    const int j2 = t & (f2 - 1), g = t >> l2;
+    buf[(((g << lw) + c) << l2) + j2] = H[((g ? rowb : rowa) + j2) * hw + c0 + c];
+  }
+  __syncthreads();
+  fft_fwd(buf, l2, 2 * W, twy, f1);
+  auto cosy = [&](int p) -> double {
+    return p < hy ? twy[p].x : (p == hy ? -1.0 : twy[ny - p].x);
+  };
+  if (c0 == 0) {  // column 0 = (DC column) + i (Nyquist column), unpacked as in fftpc_cols
+    for (int idx = threadIdx.x; idx < 2 * f2; idx += blockDim.x) {
+      const int g = idx >> l2, i0 = idx & (f2 - 1);
+      const int p = (g ? kb : ka) + (brev(i0, l2) << l1);
+      const int m = (ny - p) & (ny - 1);
+      if (p > m) continue;  // each pair once, by its smaller wavenumber
+      const int gm = (m & (f1 - 1)) == ka ? 0 : 1;
+      const int i = (g << (lw + l2)) + i0, im = (gm << (lw + l2)) + brev(m >> l1, l2);
+      const cd a = buf[i], b = buf[im];
+      const double cp = cosy(p);
+      const double s0 = sym(cp, 1.0), s1 = sym(cp, -1.0);
+      const cd A = cd{0.5 * (a.x + b.x), 0.5 * (a.y - b.y)};
+      const cd iB = cd{0.5 * (a.x - b.x), 0.5 * (a.y + b.y)};
+      buf[i] = cd{s0 * A.x + s1 * iB.x, s0 * A.y + s1 * iB.y};
+      if (m != p) buf[im] = cd{s0 * A.x - s1 * iB.x, s1 * iB.y - s0 * A.y};
+    }
+  }
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int i = idx & (f2 - 1), t = idx >> l2;
+    const int c = t & (W - 1), g = t >> lw;
+    const int q = c0 + c;
+    if (q == 0) continue;
+    const int p = (g ? kb : ka) + (brev(i, l2) << l1);
+    const double sv = sym(cosy(p), twx[q].x);
+    const cd y = buf[idx];
+    buf[idx] = cd{y.x * sv, y.y * sv};
+  }
+  __syncthreads();
+  fft_inv(buf, l2, 2 * W, twy, f1);
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int c = idx & (W - 1), t = idx >> lw;
+    const int j2 = t & (f2 - 1), g = t >> l2;
+    H[((g ? rowb : rowa) + j2) * hw + c0 + c] = buf[(((g << lw) + c) << l2) + j2];
+  }
+}
+
 int ilog2(int64_t v) {
   int l = 0;
   while ((int64_t(1) << l) < v) ++l;
@@ -338,10 +527,31 @@ void twiddles(int64_t n, double* out) {
   out[2 * (n / 4) + 1] = -1.0;
 }
 
+// The longest column kept on chip: 4096, or NKHIP_FFTPC_SPLIT where that is a power of two in
+// [16, 4096] (tests put short columns through the split path with it).
+int64_t split_length() {
+  const char* e = std::getenv("NKHIP_FFTPC_SPLIT");
+  if (!e || !*e) return 4096;
+  char* end = nullptr;
+  const long v = std::strtol(e, &end, 10);
+  if (*end || v < 16 || v > 4096 || (v & (v - 1))) return 4096;
+  return v;
+}
+
+template <class K>
+bool allow_lds(K kernel, size_t lds) {
+  if (lds <= 65536) return true;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) == hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  return false;
+}
+
 }  // namespace
 
 int fftpc_check(int64_t ny, int64_t nx, double h, double r, double k) {
-  auto pow2 = [](int64_t v) { return v >= 8 && v <= 4096 && (v & (v - 1)) == 0; };
+  auto pow2 = [](int64_t v) { return v >= 8 && v <= 16384 && (v & (v - 1)) == 0; };
   if (!pow2(ny) || !pow2(nx)) return NK_EINVAL;
   if (!(h > 0.0) || !(k > 0.0) || !std::isfinite(r) || !(k * r < 2.0)) return NK_EINVAL;
   return NK_OK;
@@ -362,14 +572,27 @@ int fftpc_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, doubl
   p->ik = 1.0 / k;
   const int64_t n2 = nx / 2;
   p->rows = int(std::max<int64_t>(1, std::min<int64_t>(ny, kRowElems / n2)));
-  // 64 KB of LDS per block of the column pass, 128 KB where two columns need it (ny = 4096)
-  p->cols = int(std::min<int64_t>(n2, std::max<int64_t>(2, std::min<int64_t>(8, 4096 / ny))));
-  const size_t lds = sizeof(cd) * size_t(ny) * size_t(p->cols);
-  if (lds > 65536 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(fftpc_cols),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return NK_EHIP;
+  // rows longer than 4096 (one row is 64 or 128 KB of LDS) and grids with more than 4096 row
+  // groups go to the kernels whose blocks take several groups in turn
+  const int64_t groups = ny / p->rows;
+  if (nx > 4096 || groups > 4096) {
+    p->row_iters = int(std::max<int64_t>(1, groups / 4096));
+    const size_t lds = sizeof(cd) * size_t(p->rows) * size_t(n2);
+    if (!allow_lds(fftpc_rows_fwd_long, lds) || !allow_lds(fftpc_rows_inv_long<false>, lds) ||
+        !allow_lds(fftpc_rows_inv_long<true>, lds))
+      return NK_EHIP;
+  }
+  if (ny > split_length()) {
+    // ny = f1 f2 with f1 = min(split, 128): 128-long sub-columns make 32-column tiles of 64 KB,
+    // and the other factor is then 64 or 128 for the lengths that need the split
+    p->l1 = ilog2(std::min<int64_t>(split_length(), 128));
+    p->l2 = p->ly - p->l1;
+    p->lw1 = ilog2(std::min<int64_t>(n2, 4096 >> p->l1));
+    p->lw2 = ilog2(std::min<int64_t>(n2, std::max(1, 2048 >> p->l2)));
+  } else {
+    // 64 KB of LDS per block of the column pass, 128 KB where two columns need it (ny = 4096)
+    p->cols = int(std::min<int64_t>(n2, std::max<int64_t>(2, std::min<int64_t>(8, 4096 / ny))));
+    if (!allow_lds(fftpc_cols, sizeof(cd) * size_t(ny) * size_t(p->cols))) return NK_EHIP;
   }
   std::vector<double> tab(size_t(nx + ny));
   twiddles(nx, tab.data());
@@ -406,7 +629,7 @@ void fftpc_destroy(FftPcPlan* p) {
   *p = FftPcPlan{};
 }
 
-// The three passes: out = IFFT2(FFT2(in) * scale / (ik - L^/2)), the transforms' 1/(nx ny) folded
+// The passes: out = IFFT2(FFT2(in) * scale / (ik - L^/2)), the transforms' 1/(nx ny) folded
 // into the symbol; with w, the last pass also leaves the block partials of w . out.
 hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, double ik, double scale,
                        const double* w, double* partial, int64_t* nblk, hipStream_t s) {
@@ -427,11 +650,35 @@ hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, double
   const size_t col_lds = sizeof(cd) * size_t(ny) * size_t(p.cols);
   const int col_threads = std::min(kColThreadsMax, std::max(64, (ny * p.cols) / 4));
   Symbol sym{p.ih2, p.r, ik, scale / (double(p.nx) * double(p.ny))};
-  fftpc_rows_fwd<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(in, H, nx, p.lx2, p.rows,
-                                                                      twx);
-  fftpc_cols<<<dim3(n2 / p.cols), dim3(col_threads), col_lds, s>>>(H, ny, n2, p.ly,
-                                                                  ilog2(p.cols), twy, twx, sym);
-  if (w)
+  const int row_blocks = int(fftpc_dot_blocks(p));
+  auto threads_for = [](int elems) { return std::min(kColThreadsMax, std::max(64, elems / 4)); };
+  if (p.row_iters)
+    fftpc_rows_fwd_long<<<dim3(row_blocks), dim3(kLongThreads), row_lds, s>>>(
+        in, H, nx, p.lx2, p.rows, p.row_iters, twx);
+  else
+    fftpc_rows_fwd<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(in, H, nx, p.lx2, p.rows,
+                                                                        twx);
+  if (p.l1) {
+    const int e1 = 1 << (p.l1 + p.lw1), e2 = 1 << (p.l2 + p.lw2 + 1);
+    const dim3 g1((n2 >> p.lw1) << p.l2), g2((n2 >> p.lw2) << (p.l1 - 1));
+    fftpc_cols_outer<false><<<g1, dim3(threads_for(e1)), sizeof(cd) * e1, s>>>(H, n2, p.l1, p.l2,
+                                                                             p.lw1, twy);
+    fftpc_cols_inner<<<g2, dim3(threads_for(e2)), sizeof(cd) * e2, s>>>(H, n2, p.l1, p.l2, p.lw2,
+                                                                      twy, twx, sym);
+    fftpc_cols_outer<true><<<g1, dim3(threads_for(e1)), sizeof(cd) * e1, s>>>(H, n2, p.l1, p.l2,
+                                                                            p.lw1, twy);
+  } else {
+    fftpc_cols<<<dim3(n2 / p.cols), dim3(col_threads), col_lds, s>>>(H, ny, n2, p.ly,
+                                                                    ilog2(p.cols), twy, twx, sym);
+  }
+  if (p.row_iters) {
+    if (w)
+      fftpc_rows_inv_long<true><<<dim3(row_blocks), dim3(kLongThreads), row_lds, s>>>(
+          H, out, nx, p.lx2, p.rows, p.row_iters, twx, w, partial);
+    else
+      fftpc_rows_inv_long<false><<<dim3(row_blocks), dim3(kLongThreads), row_lds, s>>>(
+          H, out, nx, p.lx2, p.rows, p.row_iters, twx, nullptr, nullptr);
+  } else if (w)
     fftpc_rows_inv_dot<<<dim3(ny / p.rows), dim3(kRowThreads), row_lds, s>>>(
         H, out, nx, p.lx2, p.rows, twx, w, partial);
   else

@@ -596,7 +596,7 @@ int SHProblem::set_precond(int kind) {
 
 int SHProblem::precond(const double* in, double* out) {
   if (!pc_on_) return NK_EINVAL;
-  return E_.launch(K_PRECOND, fftpc_bytes(ny_, nx_),
+  return E_.launch(K_PRECOND, fftpc_bytes(pc_),
                    [&] { return fftpc_apply(pc_, in, out, E_.s); });
 }
 

@@ -42,7 +42,7 @@ class SHProblem final : public Problem {
   void void_fused_steps(int count) override;
   // NK_PC_NONE / NK_PC_SPECTRAL (fftpc.hip: the exact inverse of the Jacobian's linear part
   // I/k - L/2).  Spectral: single slab only (no communicator), nx and ny powers of two in
-  // [8, 4096], k r < 2; NK_EINVAL otherwise, and the problem stays as it was.  The first call
+  // [8, 16384], k r < 2; NK_EINVAL otherwise, and the problem stays as it was.  The first call
   // builds the tables and takes the workspace vector from the engine; later calls only switch.
   int set_precond(int kind);
   bool has_precond() const override { return pc_on_; }

@@ -48,7 +48,8 @@ int ShLinStepper::set_precond(int kind) {
   // a refusal allocates nothing and leaves the stepper as it was
   if (fftpc_check(ny_, nx_, h_, r_, k_)) return NK_EINVAL;
   if (!pc_.tables) {
-    // the last FFT pass leaves one partial per block: at most 4096 (nx = 4096, one row each)
+    // the last FFT pass leaves one partial per block: at most 4096 (fftpc_dot_blocks; e.g.
+    // nx = 4096, one row each -- past 4096 row groups a block takes several in turn)
     if (E.partial_cap() < 4096) return NK_EINVAL;
     if (!z_) {  // z and, behind it, the half spectrum
       std::vector<double*> w;
@@ -65,7 +66,7 @@ int ShLinStepper::set_precond(int kind) {
 
 int ShLinStepper::precond(const double* r, double* z, double sigma, int64_t* nblk) {
   // ((1 + sigma) I - L k/2)^-1 = (1/k) (I (1 + sigma)/k - L/2)^-1
-  return E.launch(K_PRECOND, fftpc_dot_bytes(ny_, nx_), [&] {
+  return E.launch(K_PRECOND, fftpc_dot_bytes(pc_), [&] {
     return fftpc_apply(pc_, r, z, (1.0 + sigma) / k_, 1.0 / k_, r, E.partial(), nblk, E.s);
   });
 }

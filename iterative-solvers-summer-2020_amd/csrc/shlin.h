@@ -37,7 +37,7 @@ class ShLinStepper {
   int status() const { return status_; }
   int step(const double* U, const double* Uo, double* Unew, ShLinStats* st);
   // NK_PC_NONE: the unpreconditioned stepper, exactly.  NK_PC_SPECTRAL needs nx, ny powers of two
-  // in [8, 4096] and k r < 2 (fftpc_check); NK_EINVAL otherwise, and the stepper stays as it was.
+  // in [8, 16384] and k r < 2 (fftpc_check); NK_EINVAL otherwise, and the stepper stays as it was.
   // The first NK_PC_SPECTRAL builds the plan and allocates two vectors (z and the half spectrum);
   // no step allocates.
   int set_precond(int kind);

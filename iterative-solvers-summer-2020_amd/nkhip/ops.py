@@ -65,7 +65,7 @@ def sh13_apply(v, h, r, ny=None, nx=None, out=None):
 def sh_precond(v, h, r, k, ny=None, nx=None, out=None):
     """``M @ v`` with M the inverse of A0 = I/k - L/2 on the periodic grid, applied in Fourier
     space where A0 is diagonal: the spectral ``inner_M`` of the Swift-Hohenberg step.  nx, ny powers
-    of two in [8, 4096], k r < 2; ``out`` may be ``v``."""
+    of two in [8, 16384], k r < 2; ``out`` may be ``v``."""
     _dev(v, "v")
     ny, nx = _grid(v, ny, nx)
     out = torch.empty_like(v) if out is None else _dev(out, "out")
@@ -77,7 +77,7 @@ def sh_precond(v, h, r, k, ny=None, nx=None, out=None):
 def shlin_precond(v, h, r, k, sigma=0.0, ny=None, nx=None, dot_with=None, out=None):
     """``M @ v`` with M = ((1 + sigma) I - (k/2) L)^-1 on the periodic grid, the spectral
     preconditioner of ``SHLinearised(precond="spectral")`` (at sigma = 0: ``sh_precond(v) / k``).
-    nx, ny powers of two in [8, 4096], k r < 2, sigma >= 0; ``out`` may be ``v``.  With
+    nx, ny powers of two in [8, 16384], k r < 2, sigma >= 0; ``out`` may be ``v``.  With
     ``dot_with=w`` returns ``(z, w . z)``: the last FFT pass forms the dot itself, in a fixed
     summation order; ``z`` is the same either way."""
     _dev(v, "v")

@@ -89,7 +89,7 @@ class SwiftHohenberg:
         ``NK_PC_NONE`` (the unpreconditioned solver, exactly) or ``"spectral"`` /
         ``NK_PC_SPECTRAL``, the exact inverse of the Jacobian's linear part I/k - L/2 applied with
         hand-written FFT passes (``ops.sh_precond``).  Spectral needs a single slab (no ``comm``),
-        nx and ny powers of two in [8, 4096] and k r < 2; anything else raises and leaves the
+        nx and ny powers of two in [8, 16384] and k r < 2; anything else raises and leaves the
         stepper as it was."""
         names = {None: _lib.NK_PC_NONE, "none": _lib.NK_PC_NONE, "spectral": _lib.NK_PC_SPECTRAL}
         if isinstance(kind, str) or kind is None:

@@ -55,7 +55,7 @@ class SHLinearised:
         """Preconditioner of the CG solve: ``None`` / ``"none"`` / ``NK_PC_NONE`` (the
         unpreconditioned stepper, exactly) or ``"spectral"`` / ``NK_PC_SPECTRAL``,
         M = ((1 + sigma) I - L k/2)^-1 with sigma = max(mean(D), 0) recomputed every step.
-        Spectral needs N and ny powers of two in [8, 4096] and k r < 2; anything else raises and
+        Spectral needs N and ny powers of two in [8, 16384] and k r < 2; anything else raises and
         leaves the stepper as it was."""
         names = {None: _lib.NK_PC_NONE, "none": _lib.NK_PC_NONE, "spectral": _lib.NK_PC_SPECTRAL}
         if isinstance(kind, str) or kind is None:
