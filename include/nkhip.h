@@ -43,6 +43,10 @@ extern "C" {
 /* Preconditioner of the inner LGMRES solve (scipy newton_krylov's inner_M, lgmres's M). */
 #define NK_PC_NONE 0     /* none: the solver as it is without this option */
 #define NK_PC_SPECTRAL 1 /* the exact inverse of the linear part I/k - L/2 of the SH Jacobian */
+/* The same operator on more grids: even sides 2^a 3^b 5^c in [6, 4096] as well (mixed-radix
+ * transforms).  A separate kind because NK_PC_SPECTRAL's contract is to refuse such sides; a grid
+ * NK_PC_SPECTRAL accepts runs the same kernels, and gives the same bits, under either kind. */
+#define NK_PC_SPECTRAL_MIXED 2
 
 #define NK_JVP_FD 0       /* KrylovJacobian.matvec finite difference (scipy-faithful) */
 #define NK_JVP_ANALYTIC 1 /* exact J v = v/k - (L v + (2 g u - 3 u^2) v)/2 */
@@ -172,6 +176,13 @@ int64_t nk_arnoldi_mbox_launches(void);
  * Builds its tables and workspace per call and synchronises `stream` (a stepper keeps them). */
 int nk_sh_precond_apply(const double* v_dev, double* z_dev, int64_t ny, int64_t nx, double h,
                         double r, double k, void* stream);
+/* The same with the kind named: NK_PC_SPECTRAL is nk_sh_precond_apply; NK_PC_SPECTRAL_MIXED also
+ * takes grids whose sides are both even, of the form 2^a 3^b 5^c and in [6, 4096] (mixed-radix
+ * transforms of radix 4, 2, 3 and 5, still three passes and 48 B per point), and on a grid
+ * NK_PC_SPECTRAL accepts gives its bits.  A side with another prime factor (61, 14), an odd side,
+ * or a side above 4096 that is no power of two: NK_EINVAL. */
+int nk_sh_precond_apply_kind(const double* v_dev, double* z_dev, int64_t ny, int64_t nx, double h,
+                             double r, double k, int32_t kind, void* stream);
 
 /* ---------------- BLAS-1 (scipy get_blas_funcs dot/nrm2/axpy/scal in _gcrotmk.py:104-126) ------ */
 /* Scalar results are written to host memory; the call synchronises `stream`. */
@@ -346,9 +357,11 @@ int64_t nk_sh_workspace_bytes(nk_sh* s);
  * unpreconditioned, v0 = M F, and every Arnoldi vector is M (J z).  NK_PC_NONE restores the
  * unpreconditioned solver exactly.  NK_PC_SPECTRAL (see nk_sh_precond_apply) needs a single slab
  * (comm == NULL), nx and ny powers of two in [8, 16384] and k r < 2; NK_EINVAL otherwise, and the
- * stepper stays as it was.  The first NK_PC_SPECTRAL builds the tables and takes two vectors of
- * workspace (counted by nk_sh_workspace_bytes); no step allocates.  A preconditioned step runs
- * the host loop: one JVP pass and one application of M per Arnoldi step, no fused step. */
+ * stepper stays as it was.  NK_PC_SPECTRAL_MIXED (see nk_sh_precond_apply_kind) has the same
+ * semantics and counters on the grids of that entry, single slab only.  The first of either builds
+ * the tables and takes two vectors of workspace (counted by nk_sh_workspace_bytes); no step
+ * allocates.  A preconditioned step runs the host loop: one JVP pass and one application of M per
+ * Arnoldi step, no fused step. */
 int nk_sh_set_precond(nk_sh* s, int32_t kind);
 /* Applications of M in the last nk_sh_step (0 without a preconditioner; -1: s == NULL). */
 int64_t nk_sh_precond_applies(nk_sh* s);
@@ -443,8 +456,9 @@ int nk_shlin_step(nk_shlin* s, const double* U_dev, const double* Uo_dev, double
  *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean(D), 0)  (recomputed every step),
  * applied in Fourier space by the passes of nk_sh_precond_apply; the stopping rule is unchanged
  * (the recursive unpreconditioned residual).  Needs nx and ny powers of two in [8, 16384] and
- * k r < 2; NK_EINVAL otherwise, and the stepper stays as it was.  The first NK_PC_SPECTRAL builds
- * the tables and takes two vectors of workspace; no step allocates. */
+ * k r < 2; NK_EINVAL otherwise, and the stepper stays as it was.  NK_PC_SPECTRAL_MIXED: the same on
+ * the grids of nk_sh_precond_apply_kind.  The first of either builds the tables and takes two
+ * vectors of workspace; no step allocates. */
 int nk_shlin_set_precond(nk_shlin* s, int32_t kind);
 /* Applications of M launched in the last nk_shlin_step (iterations + 1: the one of the start, and
  * the last iteration's, queued before its residual is known; 0 without M; -1: s == NULL). */
@@ -460,12 +474,20 @@ double nk_shlin_precond_shift(nk_shlin* s);
 int nk_shlin_precond_apply(const double* v_dev, double* z_dev, int64_t ny, int64_t nx, double h,
                            double r, double k, double sigma, const double* w_dev,
                            double* dot_host, void* stream);
+/* The same with the kind named (NK_PC_SPECTRAL or NK_PC_SPECTRAL_MIXED, as
+ * nk_sh_precond_apply_kind). */
+int nk_shlin_precond_apply_kind(const double* v_dev, double* z_dev, int64_t ny, int64_t nx,
+                                double h, double r, double k, double sigma, const double* w_dev,
+                                double* dot_host, int32_t kind, void* stream);
 /* HIP-event time of one nk_shlin_precond_apply's three passes on a zero field, in milliseconds,
  * without (*ms_plain) and with (*ms_dot) the fused dot: `reps` >= 1 applications between two
  * events after one untimed application, tables and workspace built outside the timed region.
  * Synchronises `stream`.  Diagnostic only (scripts/shlin_precond_probe.py). */
 int nk_debug_shlin_precond_time(int64_t ny, int64_t nx, double h, double r, double k, double sigma,
                                 int32_t reps, double* ms_plain, double* ms_dot, void* stream);
+int nk_debug_shlin_precond_time_kind(int64_t ny, int64_t nx, double h, double r, double k,
+                                     double sigma, int32_t reps, double* ms_plain, double* ms_dot,
+                                     int32_t kind, void* stream);
 
 /* ---------------- MEMS on a moving mesh (python_work/PMA2_nk.py) ------------ */
 /* u_t = -(-Lap)^2 u - lambda/(1+u)^2 + lambda eps^(m-2)/(1+u)^m on [endl, endr]^2 (N x N), one

@@ -52,20 +52,21 @@ int reduce_call(int64_t n, int nslots, int nsum, int nv, double* out, hipStream_
 // A spectral-preconditioner plan for the length of one call: built, handed to `body`, destroyed.
 // hipErrorInvalidValue is a refusal of fftpc_apply's (alignment, aliasing): the caller's NK_EINVAL.
 template <class L>
-int with_precond_plan(int64_t ny, int64_t nx, double h, double r, double k, L&& body) {
+int with_precond_plan(int kind, int64_t ny, int64_t nx, double h, double r, double k, L&& body) {
   FftPcPlan plan;
-  if (const int rc = fftpc_create(&plan, ny, nx, h, r, k, nullptr)) return rc;
+  if (const int rc = fftpc_create(&plan, kind, ny, nx, h, r, k, nullptr)) return rc;
   const hipError_t e = body(plan);
   fftpc_destroy(&plan);
   return e == hipErrorInvalidValue ? NK_EINVAL : hip_rc(e);
 }
 
 // z = scale (I (1 + sigma)/k - L/2)^-1 v and, with w, *dot_host = w . z; synchronises s.
-int precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r, double k,
-                  double sigma, double scale, const double* w, double* dot_host, hipStream_t s) {
+int precond_apply(int kind, const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
+                  double k, double sigma, double scale, const double* w, double* dot_host,
+                  hipStream_t s) {
   if (!v || !z || (w == nullptr) != (dot_host == nullptr)) return NK_EINVAL;
   if (!(sigma >= 0.0) || !std::isfinite(sigma)) return NK_EINVAL;
-  return with_precond_plan(ny, nx, h, r, k, [&](const FftPcPlan& plan) {
+  return with_precond_plan(kind, ny, nx, h, r, k, [&](const FftPcPlan& plan) {
     double* red = nullptr;  // the block partials, then the sum
     const int64_t nb = fftpc_dot_blocks(plan);
     hipError_t e = hipSuccess;
@@ -848,7 +849,13 @@ int64_t nk_sh_precond_applies(nk_sh* s) { return s ? s->NK->precond_applies() : 
 
 int nk_sh_precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
                         double k, void* stream) {
-  return precond_apply(v, z, ny, nx, h, r, k, 0.0, 1.0, nullptr, nullptr, S(stream));  // M itself
+  return nk_sh_precond_apply_kind(v, z, ny, nx, h, r, k, NK_PC_SPECTRAL, stream);
+}
+
+int nk_sh_precond_apply_kind(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
+                             double k, int32_t kind, void* stream) {
+  return precond_apply(kind, v, z, ny, nx, h, r, k, 0.0, 1.0, nullptr, nullptr,
+                       S(stream));  // M itself
 }
 
 // ------------------------------------------------------------------------------ generic
@@ -1046,14 +1053,28 @@ double nk_shlin_precond_shift(nk_shlin* s) {
 int nk_shlin_precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
                            double k, double sigma, const double* w, double* dot_host,
                            void* stream) {
-  return precond_apply(v, z, ny, nx, h, r, k, sigma, 1.0 / k, w, dot_host, S(stream));
+  return nk_shlin_precond_apply_kind(v, z, ny, nx, h, r, k, sigma, w, dot_host, NK_PC_SPECTRAL,
+                                     stream);
+}
+
+int nk_shlin_precond_apply_kind(const double* v, double* z, int64_t ny, int64_t nx, double h,
+                                double r, double k, double sigma, const double* w,
+                                double* dot_host, int32_t kind, void* stream) {
+  return precond_apply(kind, v, z, ny, nx, h, r, k, sigma, 1.0 / k, w, dot_host, S(stream));
 }
 
 int nk_debug_shlin_precond_time(int64_t ny, int64_t nx, double h, double r, double k, double sigma,
                                 int32_t reps, double* ms_plain, double* ms_dot, void* stream) {
+  return nk_debug_shlin_precond_time_kind(ny, nx, h, r, k, sigma, reps, ms_plain, ms_dot,
+                                          NK_PC_SPECTRAL, stream);
+}
+
+int nk_debug_shlin_precond_time_kind(int64_t ny, int64_t nx, double h, double r, double k,
+                                     double sigma, int32_t reps, double* ms_plain, double* ms_dot,
+                                     int32_t kind, void* stream) {
   if (reps < 1 || !ms_plain || !ms_dot || !(sigma >= 0.0) || !std::isfinite(sigma))
     return NK_EINVAL;
-  return with_precond_plan(ny, nx, h, r, k, [&](const FftPcPlan& plan) {
+  return with_precond_plan(kind, ny, nx, h, r, k, [&](const FftPcPlan& plan) {
     const size_t n = size_t(ny * nx), len = 2 * n + size_t(fftpc_dot_blocks(plan));
     double* buf = nullptr;  // v, z, then the block partials
     hipEvent_t ev[2] = {nullptr, nullptr};

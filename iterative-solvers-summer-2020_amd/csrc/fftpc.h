@@ -7,6 +7,8 @@
 // Crank-Nicolson Jacobian: ik = 1/k, scale = 1.  The semi-implicit stepper's CG solve (shlin.cpp)
 // uses ((1 + sigma) I - L k/2)^-1 with a shift sigma chosen every step: ik = (1 + sigma)/k,
 // scale = 1/k, and the dot r . z from the last pass.
+// Sides that are powers of two (NK_PC_SPECTRAL), or even sides 2^a 3^b 5^c up to 4096
+// (NK_PC_SPECTRAL_MIXED, fftpc_mixed.hip).
 // No FFT library: three hand-written passes (rows real-to-complex, columns forward + symbol +
 // inverse on chip, rows complex-to-real), 48 B per grid point.  Columns longer than 4096 (or than
 // NKHIP_FFTPC_SPLIT, a test knob) do not fit on chip and are transformed in two factors, three
@@ -18,6 +20,15 @@
 #include <cstdint>
 
 namespace nk {
+
+// The stages of one mixed-radix transform of length n = radix[0] * ... * radix[ns-1], in the order
+// the forward (decimation in frequency) transform runs them: the 3s, the 5s, 4 while two factors of
+// 2 remain, then 2 (the odd radices first: fftpc_mixed.hip says why).  Fixed per length on the host,
+// handed to the kernels by value.
+struct FftStages {
+  int n = 0, ns = 0;
+  int radix[8] = {};  // 4 * 3^6 = 2916 has the most stages of any length <= 4096: seven
+};
 
 struct FftPcPlan {
   int64_t ny = 0, nx = 0;
@@ -34,18 +45,33 @@ struct FftPcPlan {
   // split columns, ny = 2^l1 * 2^l2 (l1 = 0: whole columns on chip); 2^lw1 / 2^lw2 columns per
   // tile of the outer (length 2^l1) and inner (length 2^l2) sub-passes
   int l1 = 0, l2 = 0, lw1 = 0, lw2 = 0;
+  // The mixed-radix family (fftpc_mixed.hip; sides 2^a 3^b 5^c, both <= 4096).  `tables` is then
+  // twx (nx complex: exp(-2 pi i j/nx), every j < nx), twy (ny complex), and the two digit-reversal
+  // tables as int32: permx (nx/2 entries) and permy (ny): the position at which the forward
+  // transform leaves wavenumber p.  rows / cols are the rows per group and the columns per tile; the
+  // last group and the last tile are ragged where ny / nx/2 is no multiple of them.
+  bool mixed = false;
+  FftStages sx{}, sy{};  // the row transform (length nx/2) and the column transform (length ny)
 };
 
 // NK_OK when the spectral preconditioner exists for this grid and these constants: nx, ny powers
 // of two in [8, 16384], h > 0, k > 0 and k r < 2 (the symbol 1/k - L^/2 >= 1/k - r/2 + 1/2 is then
 // positive); NK_EINVAL otherwise.  Host only.
 int fftpc_check(int64_t ny, int64_t nx, double h, double r, double k);
+// The same for NK_PC_SPECTRAL_MIXED: every grid fftpc_check accepts, and grids whose sides are both
+// even, of the form 2^a 3^b 5^c and in [6, 4096] (a side with another prime factor, an odd side,
+// or a side above 4096 that is no power of two: NK_EINVAL).
+int fftpc_check_mixed(int64_t ny, int64_t nx, double h, double r, double k);
 // Builds the twiddle tables on the host in long double and uploads them (synchronises).  `work`:
 // ny*nx doubles of device memory the plan uses as the half spectrum (nullptr: the plan allocates
 // and owns it).  The environment variable NKHIP_FFTPC_SPLIT (a power of two in [16, 4096], anything
 // else ignored; default 4096) is read here: the longest column kept on chip.  A longer one is
 // split as min(split, 128) times the rest.
-int fftpc_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, double k, double* work);
+// kind: NK_PC_SPECTRAL (fftpc_check) or NK_PC_SPECTRAL_MIXED (fftpc_check_mixed).  Under the mixed
+// kind a grid with both sides a power of two gets the plan of NK_PC_SPECTRAL, kernel for kernel;
+// any other grid runs wholly on the mixed-radix family.
+int fftpc_create(FftPcPlan* p, int kind, int64_t ny, int64_t nx, double h, double r, double k,
+                 double* work);
 void fftpc_destroy(FftPcPlan* p);
 // out = scale * (ik I - L/2)^-1 in, the symbol's constants given per application (three launches
 // on s, five with split columns; in == out allowed).  A shifted operator
@@ -65,10 +91,18 @@ inline hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out,
   return fftpc_apply(p, in, out, p.ik, 1.0, nullptr, nullptr, nullptr, s);
 }
 // blocks of a row pass = partial sums of an application with the dot: at most 4096 (a block
-// takes row_iters groups in turn where there are more groups than that)
+// takes row_iters groups in turn where there are more groups than that; the mixed family's last
+// block may hold fewer rows than the others and counts as one)
 inline int64_t fftpc_dot_blocks(const FftPcPlan& p) {
-  return p.rows > 0 ? p.ny / (int64_t(p.rows) * (p.row_iters > 0 ? p.row_iters : 1)) : 0;
+  const int64_t per = int64_t(p.rows) * (p.row_iters > 0 ? p.row_iters : 1);
+  return p.rows > 0 ? (p.ny + per - 1) / per : 0;
 }
+// The mixed family's halves of fftpc_create and fftpc_apply (fftpc_mixed.hip), reached through
+// them: the grid and the arguments have been checked.
+int fftpc_mixed_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, double k,
+                       double* work);
+hipError_t fftpc_mixed_apply(const FftPcPlan& p, const double* in, double* out, double ik,
+                             double scale, const double* w, double* partial, hipStream_t s);
 // algorithmic HBM bytes of one application of this plan (fftpc_dot_bytes: the last pass also
 // reads w): each pass reads and writes one vector's worth, three passes or, with split columns, five
 inline double fftpc_bytes(const FftPcPlan& p) {

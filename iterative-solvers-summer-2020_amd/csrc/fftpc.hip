@@ -36,6 +36,10 @@
 // 64 or 128 KB of LDS: one row per block of 1024 threads (fftpc_rows_*_long), whose blocks take
 // several rows in turn where there are more than 4096, so that a row pass never leaves more than
 // 4096 dot partials.
+//
+// Every kernel here is radix 2: sides that are powers of two.  Sides 2^a 3^b 5^c under
+// NK_PC_SPECTRAL_MIXED take the kernels of fftpc_mixed.hip; fftpc_create and fftpc_apply below
+// hand such a plan over.
 #include "fftpc.h"
 
 #include <algorithm>
@@ -44,28 +48,18 @@
 #include <vector>
 
 #include "../../include/nkhip.h"
+#include "fftpc_dev.h"
 #include "nk_device.h"
 
 namespace nk {
 
 namespace {
 
-using cd = double2;
-
 constexpr int kRowThreads = 256;
 constexpr int kColThreadsMax = 1024;
 constexpr int kLongThreads = 1024;  // block of the row passes that take several row groups in turn
 constexpr int kRowElems = 2048;  // complex values of LDS per block of a row pass (32 KB)
 
-__device__ __forceinline__ cd cadd(cd a, cd b) { return cd{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ cd csub(cd a, cd b) { return cd{a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ cd cmul(cd a, cd w) {
-  return cd{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x};
-}
-// a * conj(w)
-__device__ __forceinline__ cd cmulc(cd a, cd w) {
-  return cd{a.x * w.x + a.y * w.y, a.y * w.x - a.x * w.y};
-}
 __device__ __forceinline__ int brev(int k, int L) { return int(__brev(unsigned(k)) >> (32 - L)); }
 
 // nb transforms of length N = 2^L (>= 2), transform b at buf + b*N, by the whole block.
@@ -315,16 +309,6 @@ __global__ __launch_bounds__(kLongThreads) void fftpc_rows_inv_long(const cd* __
   }
 }
 
-struct Symbol {
-  double ih2, r, ik, scale;
-  // scale / A0^ from the two cosines
-  __device__ double operator()(double cp, double cq) const {
-    const double s = (2.0 * cp + 2.0 * cq - 4.0) * ih2;
-    const double lh = -s * s - 2.0 * s + (r - 1.0);
-    return scale / (ik - 0.5 * lh);
-  }
-};
-
 // Pass 2: `cols` = 2^lc whole columns per block, in place on the packed half spectrum.
 __global__ __launch_bounds__(kColThreadsMax) void fftpc_cols(cd* __restrict__ H, int ny, int n2,
                                                               int ly, int lc,
@@ -557,10 +541,29 @@ int fftpc_check(int64_t ny, int64_t nx, double h, double r, double k) {
   return NK_OK;
 }
 
-int fftpc_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, double k,
+int fftpc_check_mixed(int64_t ny, int64_t nx, double h, double r, double k) {
+  if (fftpc_check(ny, nx, h, r, k) == NK_OK) return NK_OK;  // served by the kernels of this file
+  auto smooth = [](int64_t v) {
+    if (v < 6 || v > 4096 || (v & 1)) return false;
+    for (int f : {2, 3, 5})
+      while (v % f == 0) v /= f;
+    return v == 1;
+  };
+  if (!smooth(ny) || !smooth(nx)) return NK_EINVAL;
+  if (!(h > 0.0) || !(k > 0.0) || !std::isfinite(r) || !(k * r < 2.0)) return NK_EINVAL;
+  return NK_OK;
+}
+
+int fftpc_create(FftPcPlan* p, int kind, int64_t ny, int64_t nx, double h, double r, double k,
                  double* work) {
   if (!p) return NK_EINVAL;
-  const int rc = fftpc_check(ny, nx, h, r, k);
+  if (kind != NK_PC_SPECTRAL && kind != NK_PC_SPECTRAL_MIXED) return NK_EINVAL;
+  int rc = fftpc_check(ny, nx, h, r, k);
+  // the mixed kind on a grid this file serves is this file's plan: the same launches, the same bits
+  if (rc && kind == NK_PC_SPECTRAL_MIXED) {
+    rc = fftpc_check_mixed(ny, nx, h, r, k);
+    return rc ? rc : fftpc_mixed_create(p, ny, nx, h, r, k, work);
+  }
   if (rc) return rc;
   *p = FftPcPlan{};
   p->ny = ny;
@@ -642,6 +645,7 @@ hipError_t fftpc_apply(const FftPcPlan& p, const double* in, double* out, double
   if (!(ik > 0.5 * (p.r - 1.0)) || !std::isfinite(ik) || !std::isfinite(scale))
     return hipErrorInvalidValue;  // the symbol ik - L^/2 >= ik - (r - 1)/2 must stay positive
   if (nblk) *nblk = fftpc_dot_blocks(p);
+  if (p.mixed) return fftpc_mixed_apply(p, in, out, ik, scale, w, partial, s);
   const int nx = int(p.nx), ny = int(p.ny), n2 = nx / 2;
   const cd* twx = reinterpret_cast<const cd*>(p.tables);
   const cd* twy = reinterpret_cast<const cd*>(p.tables + p.nx);

@@ -582,12 +582,16 @@ int SHProblem::set_precond(int kind) {
     pc_on_ = false;
     return NK_OK;
   }
-  if (kind != NK_PC_SPECTRAL || dist() || ny_g_ != ny_) return NK_EINVAL;
-  if (fftpc_check(ny_, nx_, h_, r_, c_.k)) return NK_EINVAL;
+  if ((kind != NK_PC_SPECTRAL && kind != NK_PC_SPECTRAL_MIXED) || dist() || ny_g_ != ny_)
+    return NK_EINVAL;
+  // a grid NK_PC_SPECTRAL accepts has one plan, whichever kind asks for it
+  const bool mixed = fftpc_check(ny_, nx_, h_, r_, c_.k) != NK_OK;
+  if (mixed && (kind != NK_PC_SPECTRAL_MIXED || fftpc_check_mixed(ny_, nx_, h_, r_, c_.k)))
+    return NK_EINVAL;
   if (!pc_.tables) {
     std::vector<double*> w;
     int rc = E_.alloc_aux(1, &w);
-    if (!rc) rc = fftpc_create(&pc_, ny_, nx_, h_, r_, c_.k, w[0]);
+    if (!rc) rc = fftpc_create(&pc_, kind, ny_, nx_, h_, r_, c_.k, w[0]);
     if (rc) return rc;
   }
   pc_on_ = true;

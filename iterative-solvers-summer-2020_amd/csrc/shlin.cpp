@@ -44,9 +44,12 @@ int ShLinStepper::set_precond(int kind) {
     pc_on_ = false;
     return NK_OK;
   }
-  if (kind != NK_PC_SPECTRAL) return NK_EINVAL;
-  // a refusal allocates nothing and leaves the stepper as it was
-  if (fftpc_check(ny_, nx_, h_, r_, k_)) return NK_EINVAL;
+  if (kind != NK_PC_SPECTRAL && kind != NK_PC_SPECTRAL_MIXED) return NK_EINVAL;
+  // a refusal allocates nothing and leaves the stepper as it was; a grid NK_PC_SPECTRAL accepts
+  // has one plan, whichever kind asks for it
+  const bool mixed = fftpc_check(ny_, nx_, h_, r_, k_) != NK_OK;
+  if (mixed && (kind != NK_PC_SPECTRAL_MIXED || fftpc_check_mixed(ny_, nx_, h_, r_, k_)))
+    return NK_EINVAL;
   if (!pc_.tables) {
     // the last FFT pass leaves one partial per block: at most 4096 (fftpc_dot_blocks; e.g.
     // nx = 4096, one row each -- past 4096 row groups a block takes several in turn)
@@ -57,7 +60,7 @@ int ShLinStepper::set_precond(int kind) {
       if (rc) return rc;
       z_ = w[0];
     }
-    const int rc = fftpc_create(&pc_, ny_, nx_, h_, r_, k_, z_ + E.npad);
+    const int rc = fftpc_create(&pc_, kind, ny_, nx_, h_, r_, k_, z_ + E.npad);
     if (rc) return rc;
   }
   pc_on_ = true;

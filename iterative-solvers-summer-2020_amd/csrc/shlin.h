@@ -38,7 +38,8 @@ class ShLinStepper {
   int step(const double* U, const double* Uo, double* Unew, ShLinStats* st);
   // NK_PC_NONE: the unpreconditioned stepper, exactly.  NK_PC_SPECTRAL needs nx, ny powers of two
   // in [8, 16384] and k r < 2 (fftpc_check); NK_EINVAL otherwise, and the stepper stays as it was.
-  // The first NK_PC_SPECTRAL builds the plan and allocates two vectors (z and the half spectrum);
+  // NK_PC_SPECTRAL_MIXED takes even sides 2^a 3^b 5^c in [6, 4096] as well (fftpc_check_mixed).
+  // The first of either builds the plan and allocates two vectors (z and the half spectrum);
   // no step allocates.
   int set_precond(int kind);
   const ShLinStats& last() const { return last_; }

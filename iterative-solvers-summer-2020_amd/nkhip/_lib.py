@@ -32,6 +32,7 @@ NK_JVP_FD = 0
 NK_JVP_ANALYTIC = 1
 NK_PC_NONE = 0
 NK_PC_SPECTRAL = 1
+NK_PC_SPECTRAL_MIXED = 2
 
 
 class nk_opts(C.Structure):
@@ -109,6 +110,7 @@ SIGNATURES = [
                                       _I64, _I64, _D, _D, _D, _D, _D, _D, _P, _P,
                                       C.POINTER(_D), _P]),
     ("nk_sh_precond_apply", C.c_int, [_P, _P, _I64, _I64, _D, _D, _D, _P]),
+    ("nk_sh_precond_apply_kind", C.c_int, [_P, _P, _I64, _I64, _D, _D, _D, _I32, _P]),
     ("nk_edge_elems", C.c_int64, [_I64, _I64]),
     ("nk_arnoldi_mbox_launches", C.c_int64, []),
     ("nk_edge_gather", C.c_int, [_P, _P, _I64, _I64, _P]),
@@ -181,8 +183,12 @@ SIGNATURES = [
     ("nk_shlin_precond_shift", C.c_double, [_P]),
     ("nk_shlin_precond_apply", C.c_int, [_P, _P, _I64, _I64, _D, _D, _D, _D, _P, C.POINTER(_D),
                                          _P]),
+    ("nk_shlin_precond_apply_kind", C.c_int, [_P, _P, _I64, _I64, _D, _D, _D, _D, _P,
+                                              C.POINTER(_D), _I32, _P]),
     ("nk_debug_shlin_precond_time", C.c_int, [_I64, _I64, _D, _D, _D, _D, _I32, C.POINTER(_D),
                                               C.POINTER(_D), _P]),
+    ("nk_debug_shlin_precond_time_kind", C.c_int, [_I64, _I64, _D, _D, _D, _D, _I32,
+                                                   C.POINTER(_D), C.POINTER(_D), _I32, _P]),
     ("nk_mems_params_default", C.c_int, [C.POINTER(nk_mems_params)]),
     ("nk_mems_create", C.c_int, [C.POINTER(_P), C.POINTER(nk_mems_params), C.POINTER(nk_opts),
                                  _P]),

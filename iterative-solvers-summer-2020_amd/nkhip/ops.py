@@ -12,6 +12,7 @@ import ctypes as C
 
 import torch
 
+from . import _lib
 from ._lib import check, lib
 
 
@@ -62,24 +63,32 @@ def sh13_apply(v, h, r, ny=None, nx=None, out=None):
     return out
 
 
-def sh_precond(v, h, r, k, ny=None, nx=None, out=None):
+def _pc_kind(mixed):
+    return _lib.NK_PC_SPECTRAL_MIXED if mixed else _lib.NK_PC_SPECTRAL
+
+
+def sh_precond(v, h, r, k, ny=None, nx=None, out=None, mixed=False):
     """``M @ v`` with M the inverse of A0 = I/k - L/2 on the periodic grid, applied in Fourier
     space where A0 is diagonal: the spectral ``inner_M`` of the Swift-Hohenberg step.  nx, ny powers
-    of two in [8, 16384], k r < 2; ``out`` may be ``v``."""
+    of two in [8, 16384], k r < 2; ``out`` may be ``v``.  ``mixed=True`` (the ``"spectral-mixed"``
+    kind) also takes grids whose sides are both even, of the form 2^a 3^b 5^c and in [6, 4096]; on a
+    grid of powers of two it gives the same bits."""
     _dev(v, "v")
     ny, nx = _grid(v, ny, nx)
     out = torch.empty_like(v) if out is None else _dev(out, "out")
-    check(lib.nk_sh_precond_apply(_ptr(v), _ptr(out), ny, nx, float(h), float(r), float(k),
-                                  _stream()), "nk_sh_precond_apply")
+    check(lib.nk_sh_precond_apply_kind(_ptr(v), _ptr(out), ny, nx, float(h), float(r), float(k),
+                                       _pc_kind(mixed), _stream()), "nk_sh_precond_apply_kind")
     return out
 
 
-def shlin_precond(v, h, r, k, sigma=0.0, ny=None, nx=None, dot_with=None, out=None):
+def shlin_precond(v, h, r, k, sigma=0.0, ny=None, nx=None, dot_with=None, out=None,
+                  mixed=False):
     """``M @ v`` with M = ((1 + sigma) I - (k/2) L)^-1 on the periodic grid, the spectral
     preconditioner of ``SHLinearised(precond="spectral")`` (at sigma = 0: ``sh_precond(v) / k``).
     nx, ny powers of two in [8, 16384], k r < 2, sigma >= 0; ``out`` may be ``v``.  With
     ``dot_with=w`` returns ``(z, w . z)``: the last FFT pass forms the dot itself, in a fixed
-    summation order; ``z`` is the same either way."""
+    summation order; ``z`` is the same either way.  ``mixed=True``: the grids of
+    ``sh_precond(..., mixed=True)``."""
     _dev(v, "v")
     ny, nx = _grid(v, ny, nx)
     out = torch.empty_like(v) if out is None else _dev(out, "out")
@@ -91,10 +100,11 @@ def shlin_precond(v, h, r, k, sigma=0.0, ny=None, nx=None, dot_with=None, out=No
         if w.numel() != v.numel():
             raise ValueError("shlin_precond: size mismatch")
         dot = C.c_double()
-    check(lib.nk_shlin_precond_apply(_ptr(v), _ptr(out), ny, nx, float(h), float(r), float(k),
-                                     float(sigma), _ptr(w) if w is not None else None,
-                                     C.byref(dot) if dot is not None else None, _stream()),
-          "nk_shlin_precond_apply")
+    check(lib.nk_shlin_precond_apply_kind(_ptr(v), _ptr(out), ny, nx, float(h), float(r), float(k),
+                                          float(sigma), _ptr(w) if w is not None else None,
+                                          C.byref(dot) if dot is not None else None,
+                                          _pc_kind(mixed), _stream()),
+          "nk_shlin_precond_apply_kind")
     return out if dot is None else (out, dot.value)
 
 

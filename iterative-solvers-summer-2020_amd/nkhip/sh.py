@@ -90,16 +90,21 @@ class SwiftHohenberg:
         ``NK_PC_SPECTRAL``, the exact inverse of the Jacobian's linear part I/k - L/2 applied with
         hand-written FFT passes (``ops.sh_precond``).  Spectral needs a single slab (no ``comm``),
         nx and ny powers of two in [8, 16384] and k r < 2; anything else raises and leaves the
-        stepper as it was."""
-        names = {None: _lib.NK_PC_NONE, "none": _lib.NK_PC_NONE, "spectral": _lib.NK_PC_SPECTRAL}
+        stepper as it was.  ``"spectral-mixed"`` / ``NK_PC_SPECTRAL_MIXED`` is the same operator on
+        more grids: sides that are both even, of the form 2^a 3^b 5^c and in [6, 4096] as well
+        (``ops.sh_precond(..., mixed=True)``); it is a name of its own because ``"spectral"``
+        refuses such sides by contract."""
+        names = {None: _lib.NK_PC_NONE, "none": _lib.NK_PC_NONE, "spectral": _lib.NK_PC_SPECTRAL,
+                 "spectral-mixed": _lib.NK_PC_SPECTRAL_MIXED}
         if isinstance(kind, str) or kind is None:
             if kind not in names:
-                raise ValueError(f"inner_M={kind!r}: None or 'spectral'")
+                raise ValueError(f"inner_M={kind!r}: None, 'spectral' or 'spectral-mixed'")
             code = names[kind]
         else:
             code = int(kind)
         check(lib.nk_sh_set_precond(self._h, code), "nk_sh_set_precond")
-        self.inner_M = "spectral" if code == _lib.NK_PC_SPECTRAL else None
+        self.inner_M = {_lib.NK_PC_SPECTRAL: "spectral",
+                        _lib.NK_PC_SPECTRAL_MIXED: "spectral-mixed"}.get(code)
 
     # ----------------------------------------------------------------------------- stepping
     def _as_grid(self, U):

@@ -56,16 +56,19 @@ class SHLinearised:
         unpreconditioned stepper, exactly) or ``"spectral"`` / ``NK_PC_SPECTRAL``,
         M = ((1 + sigma) I - L k/2)^-1 with sigma = max(mean(D), 0) recomputed every step.
         Spectral needs N and ny powers of two in [8, 16384] and k r < 2; anything else raises and
-        leaves the stepper as it was."""
-        names = {None: _lib.NK_PC_NONE, "none": _lib.NK_PC_NONE, "spectral": _lib.NK_PC_SPECTRAL}
+        leaves the stepper as it was.  ``"spectral-mixed"`` / ``NK_PC_SPECTRAL_MIXED``: the same on
+        sides that are both even, of the form 2^a 3^b 5^c and in [6, 4096] as well."""
+        names = {None: _lib.NK_PC_NONE, "none": _lib.NK_PC_NONE, "spectral": _lib.NK_PC_SPECTRAL,
+                 "spectral-mixed": _lib.NK_PC_SPECTRAL_MIXED}
         if isinstance(kind, str) or kind is None:
             if kind not in names:
-                raise ValueError(f"precond={kind!r}: None or 'spectral'")
+                raise ValueError(f"precond={kind!r}: None, 'spectral' or 'spectral-mixed'")
             code = names[kind]
         else:
             code = int(kind)
         check(lib.nk_shlin_set_precond(self._h, code), "nk_shlin_set_precond")
-        self.precond = "spectral" if code == _lib.NK_PC_SPECTRAL else None
+        self.precond = {_lib.NK_PC_SPECTRAL: "spectral",
+                        _lib.NK_PC_SPECTRAL_MIXED: "spectral-mixed"}.get(code)
 
     def close(self):
         if self._h:

@@ -67,6 +67,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--start", choices=["bench", "smooth"], default="bench")
     ap.add_argument("--maxiter", type=int, default=None)
+    ap.add_argument("--kind", choices=["spectral", "spectral-mixed"], default="spectral",
+                    help="the preconditioned leg's kind (spectral-mixed: sides 2^a 3^b 5^c)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -83,7 +85,7 @@ def main():
         U0 = torch.as_tensor(0.5 * np.cos(3 * x)[:, None] * np.sin(2 * x)[None, :],
                              device="cuda")
     res, failed = {}, []
-    for name, M in (("spectral", "spectral"), ("none (fused)", None)):
+    for name, M in (("spectral", args.kind), ("none (fused)", None)):
         v = run(nkhip, torch, U0, n, h, k, r, g, M, args.warmup, args.steps, args.profile,
                 args.maxiter)
         if "failed" in v:
@@ -101,7 +103,7 @@ def main():
         del F
     lines = [f"## precond_probe: {n} x {n}, h = {h}, k = {k}, r = {r}, g = {g}; "
              f"{args.warmup} warm-up steps, steps {args.warmup}..{args.warmup + args.steps - 1} "
-             f"timed, start = {args.start}", "",
+             f"timed, start = {args.start}, kind = {args.kind}", "",
              "| inner_M | steps/s | Arnoldi steps/step | F evaluations/step | Newton its/step | "
              "M applications/step |", "|---|---|---|---|---|---|"]
     for name, v in sorted(res.items()):

@@ -63,6 +63,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20, help="applications of M between two events")
     ap.add_argument("--maxiter", type=int, default=1000, help="of the unpreconditioned leg")
     ap.add_argument("--start", choices=["bench", "smooth"], default="bench")
+    ap.add_argument("--kind", choices=["spectral", "spectral-mixed"], default="spectral",
+                    help="the preconditioned leg's kind (spectral-mixed: sides 2^a 3^b 5^c)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -79,14 +81,15 @@ def main():
         U0 = torch.as_tensor(0.5 * np.cos(3 * x)[:, None] * np.sin(2 * x)[None, :],
                              device="cuda")
     res, failed = {}, []
-    for name, pc, mi in (("spectral", "spectral", 1000), ("none", None, args.maxiter)):
+    for name, pc, mi in (("spectral", args.kind, 1000), ("none", None, args.maxiter)):
         v = run(nkhip, torch, U0, n, h, k, r, g, pc, args.warmup, args.steps, mi)
         if "failed" in v:
             failed.append(f"precond = {name} (maxiter {mi}): {v['failed']}")
         else:
             res[name] = v
     lines = [f"## shlin_precond_probe: {n} x {n}, h = {h}, k = {k}, r = {r}, g = {g}; "
-             f"{args.warmup} warm-up steps, {args.steps} timed, start = {args.start}", "",
+             f"{args.warmup} warm-up steps, {args.steps} timed, start = {args.start}, "
+             f"kind = {args.kind}", "",
              "| precond | steps/s | CG iterations/step | M applications/step | last shift | "
              "last relative residual |", "|---|---|---|---|---|---|"]
     for name in ("none", "spectral"):
@@ -100,9 +103,12 @@ def main():
                       f"(max|U| {float(res['none']['last'].abs().max()):.3g})."]
     ms_p, ms_d = C.c_double(), C.c_double()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    nkhip._lib.check(nkhip.lib.nk_debug_shlin_precond_time(n, n, h, r, k, 0.2, args.reps,
-                                                           C.byref(ms_p), C.byref(ms_d), st),
-                     "nk_debug_shlin_precond_time")
+    kind = {"spectral": nkhip._lib.NK_PC_SPECTRAL,
+            "spectral-mixed": nkhip._lib.NK_PC_SPECTRAL_MIXED}[args.kind]
+    nkhip._lib.check(nkhip.lib.nk_debug_shlin_precond_time_kind(n, n, h, r, k, 0.2, args.reps,
+                                                                C.byref(ms_p), C.byref(ms_d),
+                                                                kind, st),
+                     "nk_debug_shlin_precond_time_kind")
     pts = float(n) * n
     lines += ["", "| one application of M (HIP events) | ms | algorithmic B/point | TB/s | "
                   "of 8 TB/s |", "|---|---|---|---|---|"]
