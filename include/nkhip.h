@@ -451,6 +451,26 @@ int nk_shlin_create(nk_shlin** out, int64_t ny, int64_t nx, double h, double r, 
 int nk_shlin_destroy(nk_shlin* s);
 int nk_shlin_step(nk_shlin* s, const double* U_dev, const double* Uo_dev, double* Unew_dev,
                   int64_t* iters, double* relres);
+/* `nsteps` steps of `batch` independent states in one launch: one workgroup per state runs what
+ * nk_shlin_step runs (diagonal, right-hand side, warm start, CG with the same stopping rule and
+ * guards, (U, Uo) <- (x, U)) with the state in registers and the search direction in LDS.  For
+ * grids with both sides >= 5 and ny nx <= nk_shlin_resident_max_points(); one GPU.  Plain CG: the
+ * call ignores nk_shlin_set_precond.  States are `batch` contiguous rows of ny nx doubles;
+ * Uprev_dev may be NULL.  r_dev, g_dev: `batch` doubles each, per-member r and g, or NULL for the
+ * stepper's own (h, k, rtol, maxiter and the grid are always the stepper's).  A member's result
+ * depends on its own inputs alone (not on the batch size, its place in it, or the run).  A
+ * member that ends a step with a status other than NK_OK stops there, its outputs its last
+ * accepted (U, Uo); the others go on.  Host arrays of `batch` entries, any of them NULL: CG
+ * iterations over the run, steps completed, relative residual of the last solve, status.  Returns
+ * the worst member status (NK_NONFINITE over NK_NO_CONVERGENCE over NK_OK); NK_EINVAL, with
+ * nothing launched and the stepper unchanged, for a grid outside the cap, batch < 1 or
+ * nsteps < 1.  Synchronises the stepper's stream. */
+int nk_shlin_run_batch(nk_shlin* s, const double* U_dev, const double* Uo_dev, double* Unew_dev,
+                       double* Uprev_dev, int64_t batch, int64_t nsteps, const double* r_dev,
+                       const double* g_dev, int64_t* iters, int64_t* steps_done, double* relres,
+                       int32_t* status);
+/* The cap of nk_shlin_run_batch in grid points (>= 9216 = 96 x 96).  Host only. */
+int64_t nk_shlin_resident_max_points(void);
 /* Preconditioner of the stepper's CG solve.  NK_PC_NONE restores the unpreconditioned stepper
  * exactly.  NK_PC_SPECTRAL: preconditioned CG with the constant-coefficient part of the matrix,
  *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean(D), 0)  (recomputed every step),

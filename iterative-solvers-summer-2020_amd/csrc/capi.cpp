@@ -1039,6 +1039,14 @@ int nk_shlin_step(nk_shlin* s, const double* U, const double* Uo, double* Unew, 
   if (relres) *relres = st.relres;
   return rc;
 }
+int nk_shlin_run_batch(nk_shlin* s, const double* U, const double* Uo, double* Unew, double* Uprev,
+                       int64_t batch, int64_t nsteps, const double* r, const double* g,
+                       int64_t* iters, int64_t* steps_done, double* relres, int32_t* status) {
+  if (!s) return NK_EINVAL;
+  return reinterpret_cast<ShLinStepper*>(s)->run_batch(U, Uo, Unew, Uprev, batch, nsteps, r, g,
+                                                       iters, steps_done, relres, status);
+}
+int64_t nk_shlin_resident_max_points(void) { return kShLinResidentMaxPoints; }
 int nk_shlin_set_precond(nk_shlin* s, int32_t kind) {
   if (!s) return NK_EINVAL;
   return reinterpret_cast<ShLinStepper*>(s)->set_precond(kind);

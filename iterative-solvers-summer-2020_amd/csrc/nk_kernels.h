@@ -187,6 +187,34 @@ hipError_t shlin_diag_launch(const double* U, const double* Uo, double k, double
 // shift of the preconditioned stepper (shlin.cpp).
 hipError_t shlin_diag_sum_launch(const double* U, const double* Uo, double k, double g, double* d,
                                  int64_t n, double* partial, hipStream_t s, int64_t* nblk);
+// Whole semi-implicit steps of small grids on chip, one workgroup per state of a batch
+// (shlin_resident.hip).  Serves ny, nx >= 5 with ny nx <= kShLinResidentMaxPoints: nine points per
+// thread of a 1024-thread block in registers, and the framed search direction of the longest such
+// grid (5 x 1843, framed 9 x 1847) in the CU's 160 KB of LDS.
+constexpr int64_t kShLinResidentMaxPoints = 9216;
+constexpr int64_t kShLinResidentMaxLds = 8 * (5 + 4) * (kShLinResidentMaxPoints / 5 + 4);
+struct ShLinResidentOut {
+  int64_t iters;   // CG iterations over the run
+  int64_t steps;   // steps completed
+  double relres;   // |b - A x| / |b| of the last solve
+  int64_t status;  // NK_OK, or what stopped the member (NK_NO_CONVERGENCE, NK_NONFINITE)
+};
+struct ShLinResidentArgs {
+  int ny = 0, nx = 0;
+  const double* U = nullptr;   // batch rows of ny nx doubles: U[s]
+  const double* Uo = nullptr;  // U[s-1]
+  double* Unew = nullptr;      // the last accepted U
+  double* Uprev = nullptr;     // the one before it (may be null)
+  const double* r = nullptr;   // per member, or null: r0
+  const double* g = nullptr;   // per member, or null: g0
+  double r0 = 0.0, g0 = 0.0;
+  double cbase = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;  // sh_coef's, the centre as c0 - r + 1
+  double k = 0.0, rtol = 0.0;
+  int64_t maxiter = 0, nsteps = 0;
+  ShLinResidentOut* out = nullptr;  // batch entries
+};
+bool shlin_resident_fits(int64_t ny, int64_t nx);
+hipError_t shlin_resident_launch(const ShLinResidentArgs& A, int64_t batch, hipStream_t s);
 // dst = src, streamed in 16-KB chunks per block (the bench's per-box bandwidth probe); n even,
 // 16-B aligned
 hipError_t stream_copy_launch(const double* src, double* dst, int64_t n, hipStream_t s);

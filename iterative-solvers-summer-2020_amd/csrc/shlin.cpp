@@ -36,7 +36,11 @@ int ShLinStepper::linop(const double* a, const double* b, double beta, const dou
                   [&] { return stencil_launch(SMode::LINOP, A, E.s, nblk); });
 }
 
-ShLinStepper::~ShLinStepper() { fftpc_destroy(&pc_); }
+ShLinStepper::~ShLinStepper() {
+  fftpc_destroy(&pc_);
+  (void)hipFree(bout_);
+  (void)hipHostFree(bout_h_);
+}
 
 int ShLinStepper::set_precond(int kind) {
   if (status_) return status_;
@@ -170,6 +174,67 @@ int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinSta
   if (st) *st = last_;
   if (rc) return rc;
   return std::isfinite(rr) ? (std::sqrt(rr) <= stop ? NK_OK : NK_NO_CONVERGENCE) : NK_NONFINITE;
+}
+
+int ShLinStepper::run_batch(const double* U, const double* Uo, double* Unew, double* Uprev,
+                            int64_t batch, int64_t nsteps, const double* r, const double* g,
+                            int64_t* iters, int64_t* steps_done, double* relres,
+                            int32_t* status) {
+  if (status_) return status_;
+  if (!U || !Uo || !Unew || batch < 1 || batch > 0x7fffffff || nsteps < 1 ||
+      !shlin_resident_fits(ny_, nx_))
+    return NK_EINVAL;
+  if (batch > bout_cap_) {  // the last call synchronised: nothing reads the old entries
+    ShLinResidentOut *d = nullptr, *h = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(*d) * batch) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(*h) * batch) != hipSuccess) {
+      (void)hipFree(d);
+      (void)hipGetLastError();
+      return NK_ENOMEM;
+    }
+    (void)hipFree(bout_);
+    (void)hipHostFree(bout_h_);
+    bout_ = d;
+    bout_h_ = h;
+    bout_cap_ = batch;
+  }
+  ShLinResidentArgs A;
+  A.ny = int(ny_);
+  A.nx = int(nx_);
+  A.U = U;
+  A.Uo = Uo;
+  A.Unew = Unew;
+  A.Uprev = Uprev;
+  A.r = r;
+  A.g = g;
+  A.r0 = r_;
+  A.g0 = g_;
+  const double e = 1.0 / (h_ * h_);
+  A.cbase = -20.0 * e * e + 8.0 * e;  // sh_coef's centre is cbase + r - 1
+  A.c1 = c_.c1;
+  A.c2 = c_.c2;
+  A.c3 = c_.c3;
+  A.k = k_;
+  A.rtol = rtol_;
+  A.maxiter = maxiter_;
+  A.nsteps = nsteps;
+  A.out = bout_;
+  hipError_t e1 = shlin_resident_launch(A, batch, E.s);
+  if (e1 == hipSuccess)
+    e1 = hipMemcpyAsync(bout_h_, bout_, sizeof(*bout_) * batch, hipMemcpyDeviceToHost, E.s);
+  if (e1 != hipSuccess) return NK_EHIP;
+  if (const int rc = E.sync()) return rc;
+  int worst = NK_OK;
+  for (int64_t b = 0; b < batch; ++b) {
+    const ShLinResidentOut& o = bout_h_[b];
+    if (iters) iters[b] = o.iters;
+    if (steps_done) steps_done[b] = o.steps;
+    if (relres) relres[b] = o.relres;
+    if (status) status[b] = int32_t(o.status);
+    if (o.status == NK_NONFINITE || (o.status == NK_NO_CONVERGENCE && worst == NK_OK))
+      worst = int(o.status);
+  }
+  return worst;
 }
 
 }  // namespace nk

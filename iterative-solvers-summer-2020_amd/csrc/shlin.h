@@ -42,6 +42,17 @@ class ShLinStepper {
   // The first of either builds the plan and allocates two vectors (z and the half spectrum);
   // no step allocates.
   int set_precond(int kind);
+  // `nsteps` steps of `batch` independent states (contiguous rows of ny nx doubles) in one launch
+  // of shlin_resident.hip: one workgroup per state runs what step() runs, on chip.  Plain CG,
+  // whatever set_precond says.  r, g: per-member device arrays, or null for the stepper's values.
+  // A member that ends a step with a status other than NK_OK stops there with its last accepted
+  // (U, Uo) in (Unew, Uprev); the others go on.  Host results per member (any may be null): CG
+  // iterations over the run, steps completed, the last solve's relative residual, status.
+  // Returns the worst member status; NK_EINVAL, with nothing launched, for a grid outside
+  // shlin_resident_fits, batch < 1 or nsteps < 1.  Synchronises.
+  int run_batch(const double* U, const double* Uo, double* Unew, double* Uprev, int64_t batch,
+                int64_t nsteps, const double* r, const double* g, int64_t* iters,
+                int64_t* steps_done, double* relres, int32_t* status);
   const ShLinStats& last() const { return last_; }
   ~ShLinStepper();
   Engine E;
@@ -61,6 +72,10 @@ class ShLinStepper {
   double* z_ = nullptr;  // M r
   bool pc_on_ = false;
   ShLinStats last_{};
+  // run_batch's per-member results: device entries and their pinned host copy, grown on demand
+  ShLinResidentOut* bout_ = nullptr;
+  ShLinResidentOut* bout_h_ = nullptr;
+  int64_t bout_cap_ = 0;
   int status_ = NK_OK;
 };
 

@@ -14,6 +14,9 @@ residual of ``rtol``.
 the matrix, M = ((1 + sigma) I - L k/2)^-1 with sigma = max(mean(D), 0), applied in Fourier space
 by hand-written FFT passes (``ops.shlin_precond``).  Off by default; off, the stepper is exactly
 the unpreconditioned one.
+
+``run_batch`` / ``step_batch`` serve small grids (ny*N <= ``resident_max_points``) and ensembles of
+them: one workgroup per state runs whole steps on chip, in one launch for the batch.
 """
 from __future__ import annotations
 
@@ -43,6 +46,8 @@ class SHLinearised:
         self.last_relres = 0.0
         self.last_precond = 0   # applications of M launched in the last step
         self.last_shift = 0.0   # sigma of the last step
+        self.last_batch = None  # per-member results of the last run_batch
+        self.last_batch_state = None  # its (U_new, U_prev): the survivors' states when it raised
         self.precond = None
         if precond is not None:
             try:
@@ -101,6 +106,59 @@ class SHLinearised:
             raise NoConvergence(out)
         raise_for_status(rc)
         return out
+
+    #: the cap of ``run_batch`` in grid points (host only; at least 96 x 96)
+    resident_max_points = int(lib.nk_shlin_resident_max_points())
+
+    def run_batch(self, U, Uo=None, nsteps=1, r=None, g=None):
+        """``nsteps`` steps of B independent states in one launch, one workgroup per state with
+        the whole CG solve on chip (csrc/shlin_resident.hip).  ``U``: (B, ny*N), or one state
+        (B = 1); ``Uo=None`` is the reference's start Uo = U (:25-26).  ``r``, ``g``: B values each
+        for a per-member sweep, or None for the stepper's own.  Returns ``(U_new, U_prev)`` as
+        (B, ny*N) tensors and fills ``last_batch`` (CPU tensors ``iters``, ``steps``, ``relres``,
+        ``status``).  Needs ny*N <= ``resident_max_points``; one GPU; plain CG -- ``set_precond``
+        has no effect here.  A member's bits depend on its own inputs alone.  A member that fails a
+        step stops with its last accepted pair; ``NoConvergence`` (carrying ``U_new``) or the
+        non-finite error is raised after ``last_batch`` is filled; ``last_batch_state`` then holds
+        ``(U_new, U_prev)``, the other members' results among them."""
+        n = self.ny * self.N
+        U = torch.as_tensor(U).to(device="cuda", dtype=torch.float64).contiguous()
+        if U.numel() == 0 or U.numel() % n or (U.dim() > 1 and U.shape[0] * n != U.numel()):
+            raise ValueError(f"expected (B, {n}) values with B >= 1, got {tuple(U.shape)}")
+        U = U.reshape(-1, n)
+        B = U.shape[0]
+        if Uo is None:
+            Uo = U
+        else:
+            Uo = torch.as_tensor(Uo).to(device="cuda", dtype=torch.float64).contiguous()
+            if Uo.numel() != U.numel():
+                raise ValueError(f"Uo: expected {U.numel()} values, got {Uo.numel()}")
+
+        def member(v, name):
+            if v is None:
+                return None
+            v = torch.as_tensor(v).to(device="cuda", dtype=torch.float64).contiguous().reshape(-1)
+            if v.numel() != B:
+                raise ValueError(f"{name}: expected {B} values, got {v.numel()}")
+            return v
+
+        r, g = member(r, "r"), member(g, "g")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        new, prev = torch.empty_like(U), torch.empty_like(U)
+        res = {"iters": torch.zeros(B, dtype=torch.int64), "steps": torch.zeros(B, dtype=torch.int64),
+               "relres": torch.zeros(B, dtype=torch.float64),
+               "status": torch.zeros(B, dtype=torch.int32)}
+        rc = lib.nk_shlin_run_batch(self._h, ptr(U), ptr(Uo), ptr(new), ptr(prev), B, int(nsteps),
+                                    ptr(r), ptr(g), ptr(res["iters"]), ptr(res["steps"]),
+                                    ptr(res["relres"]), ptr(res["status"]))
+        check(min(rc, 0), "nk_shlin_run_batch")
+        self.last_batch, self.last_batch_state = res, (new, prev)
+        raise_for_status(rc, new)
+        return new, prev
+
+    def step_batch(self, U, Uo, r=None, g=None):
+        """One step of every member: ``run_batch(U, Uo, 1, r, g)[0]``."""
+        return self.run_batch(U, Uo, 1, r, g)[0]
 
     def run(self, U0, nsteps):
         """main()'s loop from Uo = U = U0 (:25-26, :46-56); returns [U[1], ..., U[nsteps]]."""
