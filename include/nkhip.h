@@ -455,7 +455,8 @@ int nk_shlin_step(nk_shlin* s, const double* U_dev, const double* Uo_dev, double
  * nk_shlin_step runs (diagonal, right-hand side, warm start, CG with the same stopping rule and
  * guards, (U, Uo) <- (x, U)) with the state in registers and the search direction in LDS.  For
  * grids with both sides >= 5 and ny nx <= nk_shlin_resident_max_points(); one GPU.  Plain CG: the
- * call ignores nk_shlin_set_precond.  States are `batch` contiguous rows of ny nx doubles;
+ * call ignores nk_shlin_set_precond (nk_shlin_run_batch_pc takes the preconditioner as an
+ * argument).  States are `batch` contiguous rows of ny nx doubles;
  * Uprev_dev may be NULL.  r_dev, g_dev: `batch` doubles each, per-member r and g, or NULL for the
  * stepper's own (h, k, rtol, maxiter and the grid are always the stepper's).  A member's result
  * depends on its own inputs alone (not on the batch size, its place in it, or the run).  A
@@ -471,6 +472,28 @@ int nk_shlin_run_batch(nk_shlin* s, const double* U_dev, const double* Uo_dev, d
                        int32_t* status);
 /* The cap of nk_shlin_run_batch in grid points (>= 9216 = 96 x 96).  Host only. */
 int64_t nk_shlin_resident_max_points(void);
+/* nk_shlin_run_batch with the preconditioner of the CG solve named by the call (and by nothing
+ * else: nk_shlin_set_precond has no effect here either).  kind NK_PC_NONE is nk_shlin_run_batch,
+ * exactly, with zeros in the two extra arrays.  NK_PC_SPECTRAL: every member runs the
+ * preconditioned CG of nk_shlin_step under nk_shlin_set_precond(NK_PC_SPECTRAL),
+ *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean(D), 0)  per member and step,
+ * with the 2-D FFT, the symbol and the FFT back run inside the resident workgroup: the same
+ * stopping rule, guards (p.Ap <= 0, r.Mr <= 0 and non-finite data end the member with
+ * NK_NONFINITE) and per-member semantics as above.  A member whose own k r >= 2 ends with
+ * NK_NONFINITE before its first step, its outputs its inputs.  For nx and ny powers of two in
+ * [8, 128] with ny nx <= nk_shlin_resident_precond_max_points() and k r < 2 for the stepper's r;
+ * NK_EINVAL, with nothing launched or allocated and the stepper unchanged, otherwise and for any
+ * other kind (NK_PC_SPECTRAL_MIXED included).  applies, shift: host arrays of `batch` entries,
+ * either may be NULL: applications of M over the run (one per CG iteration) and sigma of the
+ * member's last solve. */
+int nk_shlin_run_batch_pc(nk_shlin* s, const double* U_dev, const double* Uo_dev,
+                          double* Unew_dev, double* Uprev_dev, int64_t batch, int64_t nsteps,
+                          const double* r_dev, const double* g_dev, int32_t kind, int64_t* iters,
+                          int64_t* steps_done, double* relres, int32_t* status, int64_t* applies,
+                          double* shift);
+/* The cap of nk_shlin_run_batch_pc with NK_PC_SPECTRAL in grid points (8192 = 128 x 64).  Host
+ * only. */
+int64_t nk_shlin_resident_precond_max_points(void);
 /* Preconditioner of the stepper's CG solve.  NK_PC_NONE restores the unpreconditioned stepper
  * exactly.  NK_PC_SPECTRAL: preconditioned CG with the constant-coefficient part of the matrix,
  *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean(D), 0)  (recomputed every step),

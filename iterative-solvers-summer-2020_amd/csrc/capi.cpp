@@ -1047,6 +1047,16 @@ int nk_shlin_run_batch(nk_shlin* s, const double* U, const double* Uo, double* U
                                                        iters, steps_done, relres, status);
 }
 int64_t nk_shlin_resident_max_points(void) { return kShLinResidentMaxPoints; }
+int nk_shlin_run_batch_pc(nk_shlin* s, const double* U, const double* Uo, double* Unew,
+                          double* Uprev, int64_t batch, int64_t nsteps, const double* r,
+                          const double* g, int32_t kind, int64_t* iters, int64_t* steps_done,
+                          double* relres, int32_t* status, int64_t* applies, double* shift) {
+  if (!s) return NK_EINVAL;
+  return reinterpret_cast<ShLinStepper*>(s)->run_batch_pc(U, Uo, Unew, Uprev, batch, nsteps, r, g,
+                                                          kind, iters, steps_done, relres, status,
+                                                          applies, shift);
+}
+int64_t nk_shlin_resident_precond_max_points(void) { return kShLinResidentPcMaxPoints; }
 int nk_shlin_set_precond(nk_shlin* s, int32_t kind) {
   if (!s) return NK_EINVAL;
   return reinterpret_cast<ShLinStepper*>(s)->set_precond(kind);

@@ -215,6 +215,25 @@ struct ShLinResidentArgs {
 };
 bool shlin_resident_fits(int64_t ny, int64_t nx);
 hipError_t shlin_resident_launch(const ShLinResidentArgs& A, int64_t batch, hipStream_t s);
+// The same steps with the spectral preconditioner M = ((1 + sigma) I - L k/2)^-1 applied on chip
+// (shlin_resident_pc.hip): preconditioned CG as ShLinStepper::step runs it with NK_PC_SPECTRAL.
+// Serves ny, nx powers of two in [8, 128] with ny nx <= kShLinResidentPcMaxPoints: the framed
+// plane and the half spectrum of a 128 x 64 grid are 139 KB of the CU's 160 KB of LDS.
+constexpr int64_t kShLinResidentPcMaxPoints = 8192;
+struct ShLinResidentPcOut {
+  int64_t applies;  // applications of M over the run
+  double shift;     // sigma of the last solve
+};
+struct ShLinResidentPcArgs {
+  ShLinResidentArgs a;
+  const double* tables = nullptr;  // shlin_resident_pc_tables: nx + ny doubles
+  double ih2 = 0.0;                // 1 / h^2
+  ShLinResidentPcOut* out = nullptr;  // batch entries
+};
+bool shlin_resident_pc_fits(int64_t ny, int64_t nx);
+// exp(-2 pi i j / nx), j < nx/2, then exp(-2 pi i j / ny), j < ny/2 (host, nx + ny doubles)
+void shlin_resident_pc_tables(int64_t ny, int64_t nx, double* out);
+hipError_t shlin_resident_pc_launch(const ShLinResidentPcArgs& P, int64_t batch, hipStream_t s);
 // dst = src, streamed in 16-KB chunks per block (the bench's per-box bandwidth probe); n even,
 // 16-B aligned
 hipError_t stream_copy_launch(const double* src, double* dst, int64_t n, hipStream_t s);

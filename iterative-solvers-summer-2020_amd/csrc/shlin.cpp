@@ -40,6 +40,9 @@ ShLinStepper::~ShLinStepper() {
   fftpc_destroy(&pc_);
   (void)hipFree(bout_);
   (void)hipHostFree(bout_h_);
+  (void)hipFree(bpc_);
+  (void)hipHostFree(bpc_h_);
+  (void)hipFree(rtab_);
 }
 
 int ShLinStepper::set_precond(int kind) {
@@ -176,54 +179,51 @@ int ShLinStepper::step(const double* U, const double* Uo, double* Unew, ShLinSta
   return std::isfinite(rr) ? (std::sqrt(rr) <= stop ? NK_OK : NK_NO_CONVERGENCE) : NK_NONFINITE;
 }
 
-int ShLinStepper::run_batch(const double* U, const double* Uo, double* Unew, double* Uprev,
-                            int64_t batch, int64_t nsteps, const double* r, const double* g,
-                            int64_t* iters, int64_t* steps_done, double* relres,
-                            int32_t* status) {
-  if (status_) return status_;
-  if (!U || !Uo || !Unew || batch < 1 || batch > 0x7fffffff || nsteps < 1 ||
-      !shlin_resident_fits(ny_, nx_))
-    return NK_EINVAL;
-  if (batch > bout_cap_) {  // the last call synchronised: nothing reads the old entries
-    ShLinResidentOut *d = nullptr, *h = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(*d) * batch) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(*h) * batch) != hipSuccess) {
-      (void)hipFree(d);
-      (void)hipGetLastError();
-      return NK_ENOMEM;
-    }
-    (void)hipFree(bout_);
-    (void)hipHostFree(bout_h_);
-    bout_ = d;
-    bout_h_ = h;
-    bout_cap_ = batch;
+// The per-member results of a batch: device entries and their pinned host copy, grown on demand.
+int ShLinStepper::grow_batch_out(int64_t batch) {
+  if (batch <= bout_cap_) return NK_OK;  // the last call synchronised: nothing reads the old entries
+  ShLinResidentOut *d = nullptr, *h = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(*d) * batch) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(*h) * batch) != hipSuccess) {
+    (void)hipFree(d);
+    (void)hipGetLastError();
+    return NK_ENOMEM;
   }
-  ShLinResidentArgs A;
-  A.ny = int(ny_);
-  A.nx = int(nx_);
-  A.U = U;
-  A.Uo = Uo;
-  A.Unew = Unew;
-  A.Uprev = Uprev;
-  A.r = r;
-  A.g = g;
-  A.r0 = r_;
-  A.g0 = g_;
+  (void)hipFree(bout_);
+  (void)hipHostFree(bout_h_);
+  bout_ = d;
+  bout_h_ = h;
+  bout_cap_ = batch;
+  return NK_OK;
+}
+
+void ShLinStepper::resident_args(ShLinResidentArgs* A, const double* U, const double* Uo,
+                                 double* Unew, double* Uprev, int64_t nsteps, const double* r,
+                                 const double* g) const {
+  A->ny = int(ny_);
+  A->nx = int(nx_);
+  A->U = U;
+  A->Uo = Uo;
+  A->Unew = Unew;
+  A->Uprev = Uprev;
+  A->r = r;
+  A->g = g;
+  A->r0 = r_;
+  A->g0 = g_;
   const double e = 1.0 / (h_ * h_);
-  A.cbase = -20.0 * e * e + 8.0 * e;  // sh_coef's centre is cbase + r - 1
-  A.c1 = c_.c1;
-  A.c2 = c_.c2;
-  A.c3 = c_.c3;
-  A.k = k_;
-  A.rtol = rtol_;
-  A.maxiter = maxiter_;
-  A.nsteps = nsteps;
-  A.out = bout_;
-  hipError_t e1 = shlin_resident_launch(A, batch, E.s);
-  if (e1 == hipSuccess)
-    e1 = hipMemcpyAsync(bout_h_, bout_, sizeof(*bout_) * batch, hipMemcpyDeviceToHost, E.s);
-  if (e1 != hipSuccess) return NK_EHIP;
-  if (const int rc = E.sync()) return rc;
+  A->cbase = -20.0 * e * e + 8.0 * e;  // sh_coef's centre is cbase + r - 1
+  A->c1 = c_.c1;
+  A->c2 = c_.c2;
+  A->c3 = c_.c3;
+  A->k = k_;
+  A->rtol = rtol_;
+  A->maxiter = maxiter_;
+  A->nsteps = nsteps;
+  A->out = bout_;
+}
+
+int ShLinStepper::collect_batch(int64_t batch, int64_t* iters, int64_t* steps_done, double* relres,
+                                int32_t* status) const {
   int worst = NK_OK;
   for (int64_t b = 0; b < batch; ++b) {
     const ShLinResidentOut& o = bout_h_[b];
@@ -235,6 +235,92 @@ int ShLinStepper::run_batch(const double* U, const double* Uo, double* Unew, dou
       worst = int(o.status);
   }
   return worst;
+}
+
+int ShLinStepper::run_batch(const double* U, const double* Uo, double* Unew, double* Uprev,
+                            int64_t batch, int64_t nsteps, const double* r, const double* g,
+                            int64_t* iters, int64_t* steps_done, double* relres,
+                            int32_t* status) {
+  if (status_) return status_;
+  if (!U || !Uo || !Unew || batch < 1 || batch > 0x7fffffff || nsteps < 1 ||
+      !shlin_resident_fits(ny_, nx_))
+    return NK_EINVAL;
+  if (const int rc = grow_batch_out(batch)) return rc;
+  ShLinResidentArgs A;
+  resident_args(&A, U, Uo, Unew, Uprev, nsteps, r, g);
+  hipError_t e1 = shlin_resident_launch(A, batch, E.s);
+  if (e1 == hipSuccess)
+    e1 = hipMemcpyAsync(bout_h_, bout_, sizeof(*bout_) * batch, hipMemcpyDeviceToHost, E.s);
+  if (e1 != hipSuccess) return NK_EHIP;
+  if (const int rc = E.sync()) return rc;
+  return collect_batch(batch, iters, steps_done, relres, status);
+}
+
+int ShLinStepper::run_batch_pc(const double* U, const double* Uo, double* Unew, double* Uprev,
+                               int64_t batch, int64_t nsteps, const double* r, const double* g,
+                               int kind, int64_t* iters, int64_t* steps_done, double* relres,
+                               int32_t* status, int64_t* applies, double* shift) {
+  if (status_) return status_;
+  if (kind == NK_PC_NONE) {
+    const int rc = run_batch(U, Uo, Unew, Uprev, batch, nsteps, r, g, iters, steps_done, relres,
+                             status);
+    for (int64_t b = 0; rc >= 0 && b < batch; ++b) {
+      if (applies) applies[b] = 0;
+      if (shift) shift[b] = 0.0;
+    }
+    return rc;
+  }
+  // refusals come before anything is launched or allocated
+  if (kind != NK_PC_SPECTRAL || !U || !Uo || !Unew || batch < 1 || batch > 0x7fffffff ||
+      nsteps < 1 || !shlin_resident_pc_fits(ny_, nx_) || fftpc_check(ny_, nx_, h_, r_, k_))
+    return NK_EINVAL;
+  if (!rtab_) {
+    std::vector<double> tab(size_t(nx_ + ny_));
+    shlin_resident_pc_tables(ny_, nx_, tab.data());
+    double* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * tab.size()) != hipSuccess) {
+      (void)hipGetLastError();
+      return NK_ENOMEM;
+    }
+    if (hipMemcpy(d, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) !=
+        hipSuccess) {
+      (void)hipFree(d);
+      return NK_EHIP;
+    }
+    rtab_ = d;
+  }
+  if (const int rc = grow_batch_out(batch)) return rc;
+  if (batch > bpc_cap_) {
+    ShLinResidentPcOut *d = nullptr, *h = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(*d) * batch) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(*h) * batch) != hipSuccess) {
+      (void)hipFree(d);
+      (void)hipGetLastError();
+      return NK_ENOMEM;
+    }
+    (void)hipFree(bpc_);
+    (void)hipHostFree(bpc_h_);
+    bpc_ = d;
+    bpc_h_ = h;
+    bpc_cap_ = batch;
+  }
+  ShLinResidentPcArgs P;
+  resident_args(&P.a, U, Uo, Unew, Uprev, nsteps, r, g);
+  P.tables = rtab_;
+  P.ih2 = 1.0 / (h_ * h_);
+  P.out = bpc_;
+  hipError_t e1 = shlin_resident_pc_launch(P, batch, E.s);
+  if (e1 == hipSuccess)
+    e1 = hipMemcpyAsync(bout_h_, bout_, sizeof(*bout_) * batch, hipMemcpyDeviceToHost, E.s);
+  if (e1 == hipSuccess)
+    e1 = hipMemcpyAsync(bpc_h_, bpc_, sizeof(*bpc_) * batch, hipMemcpyDeviceToHost, E.s);
+  if (e1 != hipSuccess) return NK_EHIP;
+  if (const int rc = E.sync()) return rc;
+  for (int64_t b = 0; b < batch; ++b) {
+    if (applies) applies[b] = bpc_h_[b].applies;
+    if (shift) shift[b] = bpc_h_[b].shift;
+  }
+  return collect_batch(batch, iters, steps_done, relres, status);
 }
 
 }  // namespace nk

@@ -44,7 +44,8 @@ class ShLinStepper {
   int set_precond(int kind);
   // `nsteps` steps of `batch` independent states (contiguous rows of ny nx doubles) in one launch
   // of shlin_resident.hip: one workgroup per state runs what step() runs, on chip.  Plain CG,
-  // whatever set_precond says.  r, g: per-member device arrays, or null for the stepper's values.
+  // whatever set_precond says (run_batch_pc below takes the preconditioner as an argument).
+  // r, g: per-member device arrays, or null for the stepper's values.
   // A member that ends a step with a status other than NK_OK stops there with its last accepted
   // (U, Uo) in (Unew, Uprev); the others go on.  Host results per member (any may be null): CG
   // iterations over the run, steps completed, the last solve's relative residual, status.
@@ -53,6 +54,17 @@ class ShLinStepper {
   int run_batch(const double* U, const double* Uo, double* Unew, double* Uprev, int64_t batch,
                 int64_t nsteps, const double* r, const double* g, int64_t* iters,
                 int64_t* steps_done, double* relres, int32_t* status);
+  // run_batch with the preconditioner named by the call.  NK_PC_NONE: run_batch, exactly (applies
+  // and shift are zeros).  NK_PC_SPECTRAL: preconditioned CG with M applied on chip
+  // (shlin_resident_pc.hip), for ny, nx powers of two in [8, 128] with ny nx <=
+  // kShLinResidentPcMaxPoints and k r < 2.  A member whose own k r_m >= 2 ends with NK_NONFINITE
+  // before its first step.  applies, shift (host, may be null): applications of M over the run and
+  // sigma of the last solve, per member.  Any other kind or grid: NK_EINVAL, nothing launched or
+  // allocated.  The first spectral call allocates the twiddle table (nx + ny doubles).
+  int run_batch_pc(const double* U, const double* Uo, double* Unew, double* Uprev, int64_t batch,
+                   int64_t nsteps, const double* r, const double* g, int kind, int64_t* iters,
+                   int64_t* steps_done, double* relres, int32_t* status, int64_t* applies,
+                   double* shift);
   const ShLinStats& last() const { return last_; }
   ~ShLinStepper();
   Engine E;
@@ -76,6 +88,16 @@ class ShLinStepper {
   ShLinResidentOut* bout_ = nullptr;
   ShLinResidentOut* bout_h_ = nullptr;
   int64_t bout_cap_ = 0;
+  // run_batch_pc's: the second per-member record, and the twiddle table of the resident kernel
+  ShLinResidentPcOut* bpc_ = nullptr;
+  ShLinResidentPcOut* bpc_h_ = nullptr;
+  int64_t bpc_cap_ = 0;
+  double* rtab_ = nullptr;
+  int grow_batch_out(int64_t batch);
+  void resident_args(ShLinResidentArgs* A, const double* U, const double* Uo, double* Unew,
+                     double* Uprev, int64_t nsteps, const double* r, const double* g) const;
+  int collect_batch(int64_t batch, int64_t* iters, int64_t* steps_done, double* relres,
+                    int32_t* status) const;
   int status_ = NK_OK;
 };
 

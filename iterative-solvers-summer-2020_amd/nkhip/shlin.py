@@ -16,7 +16,9 @@ by hand-written FFT passes (``ops.shlin_precond``).  Off by default; off, the st
 the unpreconditioned one.
 
 ``run_batch`` / ``step_batch`` serve small grids (ny*N <= ``resident_max_points``) and ensembles of
-them: one workgroup per state runs whole steps on chip, in one launch for the batch.
+them: one workgroup per state runs whole steps on chip, in one launch for the batch.  Their own
+``precond="spectral"`` applies the same preconditioner inside the resident workgroup (N and ny
+powers of two in [8, 128], ny*N <= ``resident_precond_max_points``).
 """
 from __future__ import annotations
 
@@ -110,17 +112,32 @@ class SHLinearised:
     #: the cap of ``run_batch`` in grid points (host only; at least 96 x 96)
     resident_max_points = int(lib.nk_shlin_resident_max_points())
 
-    def run_batch(self, U, Uo=None, nsteps=1, r=None, g=None):
+    #: the cap of ``run_batch(..., precond="spectral")`` in grid points (host only; 128 x 64)
+    resident_precond_max_points = int(lib.nk_shlin_resident_precond_max_points())
+
+    def run_batch(self, U, Uo=None, nsteps=1, r=None, g=None, precond=None):
         """``nsteps`` steps of B independent states in one launch, one workgroup per state with
         the whole CG solve on chip (csrc/shlin_resident.hip).  ``U``: (B, ny*N), or one state
         (B = 1); ``Uo=None`` is the reference's start Uo = U (:25-26).  ``r``, ``g``: B values each
         for a per-member sweep, or None for the stepper's own.  Returns ``(U_new, U_prev)`` as
         (B, ny*N) tensors and fills ``last_batch`` (CPU tensors ``iters``, ``steps``, ``relres``,
-        ``status``).  Needs ny*N <= ``resident_max_points``; one GPU; plain CG -- ``set_precond``
-        has no effect here.  A member's bits depend on its own inputs alone.  A member that fails a
-        step stops with its last accepted pair; ``NoConvergence`` (carrying ``U_new``) or the
-        non-finite error is raised after ``last_batch`` is filled; ``last_batch_state`` then holds
-        ``(U_new, U_prev)``, the other members' results among them."""
+        ``status``, and ``precond`` / ``shift``: applications of M over the run and sigma of the
+        last solve, zeros on the plain path).  Needs ny*N <= ``resident_max_points``; one GPU.
+
+        ``precond``: ``None`` / ``"none"`` is plain CG, and ``set_precond`` has no effect here:
+        only this argument selects the solve.  ``"spectral"`` runs the preconditioned CG of
+        ``step`` under ``precond="spectral"`` with the FFT preconditioner applied inside the
+        resident workgroup (csrc/shlin_resident_pc.hip): the iteration count no longer grows as the
+        mesh is refined.  It needs N and ny powers of two in [8, 128], ny*N <=
+        ``resident_precond_max_points`` and k r < 2 (anything else raises and leaves the stepper
+        usable); a member whose own k r >= 2 stops as a non-finite one does.
+
+        A member's bits depend on its own inputs alone.  A member that fails a step stops with its
+        last accepted pair; ``NoConvergence`` (carrying ``U_new``) or the non-finite error is
+        raised after ``last_batch`` is filled; ``last_batch_state`` then holds ``(U_new, U_prev)``,
+        the other members' results among them."""
+        if precond not in (None, "none", "spectral"):
+            raise ValueError(f"precond={precond!r}: None, 'none' or 'spectral'")
         n = self.ny * self.N
         U = torch.as_tensor(U).to(device="cuda", dtype=torch.float64).contiguous()
         if U.numel() == 0 or U.numel() % n or (U.dim() > 1 and U.shape[0] * n != U.numel()):
@@ -147,18 +164,28 @@ class SHLinearised:
         new, prev = torch.empty_like(U), torch.empty_like(U)
         res = {"iters": torch.zeros(B, dtype=torch.int64), "steps": torch.zeros(B, dtype=torch.int64),
                "relres": torch.zeros(B, dtype=torch.float64),
-               "status": torch.zeros(B, dtype=torch.int32)}
-        rc = lib.nk_shlin_run_batch(self._h, ptr(U), ptr(Uo), ptr(new), ptr(prev), B, int(nsteps),
-                                    ptr(r), ptr(g), ptr(res["iters"]), ptr(res["steps"]),
-                                    ptr(res["relres"]), ptr(res["status"]))
-        check(min(rc, 0), "nk_shlin_run_batch")
+               "status": torch.zeros(B, dtype=torch.int32),
+               "precond": torch.zeros(B, dtype=torch.int64),
+               "shift": torch.zeros(B, dtype=torch.float64)}
+        if precond == "spectral":
+            rc = lib.nk_shlin_run_batch_pc(self._h, ptr(U), ptr(Uo), ptr(new), ptr(prev), B,
+                                           int(nsteps), ptr(r), ptr(g), _lib.NK_PC_SPECTRAL,
+                                           ptr(res["iters"]), ptr(res["steps"]),
+                                           ptr(res["relres"]), ptr(res["status"]),
+                                           ptr(res["precond"]), ptr(res["shift"]))
+            check(min(rc, 0), "nk_shlin_run_batch_pc")
+        else:
+            rc = lib.nk_shlin_run_batch(self._h, ptr(U), ptr(Uo), ptr(new), ptr(prev), B,
+                                        int(nsteps), ptr(r), ptr(g), ptr(res["iters"]),
+                                        ptr(res["steps"]), ptr(res["relres"]), ptr(res["status"]))
+            check(min(rc, 0), "nk_shlin_run_batch")
         self.last_batch, self.last_batch_state = res, (new, prev)
         raise_for_status(rc, new)
         return new, prev
 
-    def step_batch(self, U, Uo, r=None, g=None):
-        """One step of every member: ``run_batch(U, Uo, 1, r, g)[0]``."""
-        return self.run_batch(U, Uo, 1, r, g)[0]
+    def step_batch(self, U, Uo, r=None, g=None, precond=None):
+        """One step of every member: ``run_batch(U, Uo, 1, r, g, precond)[0]``."""
+        return self.run_batch(U, Uo, 1, r, g, precond)[0]
 
     def run(self, U0, nsteps):
         """main()'s loop from Uo = U = U0 (:25-26, :46-56); returns [U[1], ..., U[nsteps]]."""
