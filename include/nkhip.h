@@ -483,9 +483,14 @@ int64_t nk_shlin_resident_max_points(void);
  * NK_NONFINITE before its first step, its outputs its inputs.  For nx and ny powers of two in
  * [8, 128] with ny nx <= nk_shlin_resident_precond_max_points() and k r < 2 for the stepper's r;
  * NK_EINVAL, with nothing launched or allocated and the stepper unchanged, otherwise and for any
- * other kind (NK_PC_SPECTRAL_MIXED included).  applies, shift: host arrays of `batch` entries,
- * either may be NULL: applications of M over the run (one per CG iteration) and sigma of the
- * member's last solve. */
+ * other kind.  NK_PC_SPECTRAL_MIXED: the same solve, M, sigma, stopping rule, guards and counters
+ * on grids whose sides are both even, of the form 2^a 3^b 5^c and in [6, 128], at least one of
+ * them no power of two, with ny nx <= nk_shlin_resident_precond_mixed_max_points(), a workgroup's
+ * LDS enough for the grid (every such grid up to 96 x 96, 128 x 72 and 72 x 128 among them) and
+ * k r < 2.  A grid whose sides are both powers of two is NK_PC_SPECTRAL's and gets NK_EINVAL under
+ * this kind, like every other grid outside the list.  applies, shift: host arrays of `batch`
+ * entries, either may be NULL: applications of M over the run (one per CG iteration) and sigma of
+ * the member's last solve. */
 int nk_shlin_run_batch_pc(nk_shlin* s, const double* U_dev, const double* Uo_dev,
                           double* Unew_dev, double* Uprev_dev, int64_t batch, int64_t nsteps,
                           const double* r_dev, const double* g_dev, int32_t kind, int64_t* iters,
@@ -494,6 +499,9 @@ int nk_shlin_run_batch_pc(nk_shlin* s, const double* U_dev, const double* Uo_dev
 /* The cap of nk_shlin_run_batch_pc with NK_PC_SPECTRAL in grid points (8192 = 128 x 64).  Host
  * only. */
 int64_t nk_shlin_resident_precond_max_points(void);
+/* The cap of nk_shlin_run_batch_pc with NK_PC_SPECTRAL_MIXED in grid points (9216 = 96 x 96).
+ * Host only. */
+int64_t nk_shlin_resident_precond_mixed_max_points(void);
 /* Preconditioner of the stepper's CG solve.  NK_PC_NONE restores the unpreconditioned stepper
  * exactly.  NK_PC_SPECTRAL: preconditioned CG with the constant-coefficient part of the matrix,
  *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean(D), 0)  (recomputed every step),

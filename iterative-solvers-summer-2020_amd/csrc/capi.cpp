@@ -1057,6 +1057,9 @@ int nk_shlin_run_batch_pc(nk_shlin* s, const double* U, const double* Uo, double
                                                           applies, shift);
 }
 int64_t nk_shlin_resident_precond_max_points(void) { return kShLinResidentPcMaxPoints; }
+int64_t nk_shlin_resident_precond_mixed_max_points(void) {
+  return kShLinResidentPcMixedMaxPoints;
+}
 int nk_shlin_set_precond(nk_shlin* s, int32_t kind) {
   if (!s) return NK_EINVAL;
   return reinterpret_cast<ShLinStepper*>(s)->set_precond(kind);

@@ -103,6 +103,13 @@ int fftpc_mixed_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r,
                        double* work);
 hipError_t fftpc_mixed_apply(const FftPcPlan& p, const double* in, double* out, double ik,
                              double scale, const double* w, double* partial, hipStream_t s);
+// The mixed family's host tables, also built by the resident kernel of shlin_resident_pcm.hip:
+// the stages of a length (n = 2^a 3^b 5^c), perm[p] = the position at which the forward transform
+// leaves wavenumber p (st.n entries), and exp(-2 pi i j/n) for every j < n (n even; 2 n doubles,
+// long double rounded once, the roots on the axes exact).
+FftStages fftpc_stages_of(int n);
+void fftpc_digit_reversal(const FftStages& st, int32_t* perm);
+void fftpc_roots(int64_t n, double* out);
 // algorithmic HBM bytes of one application of this plan (fftpc_dot_bytes: the last pass also
 // reads w): each pass reads and writes one vector's worth, three passes or, with split columns, five
 inline double fftpc_bytes(const FftPcPlan& p) {

@@ -53,59 +53,6 @@ constexpr int kRowThreads = 256;
 constexpr int kColThreadsMax = 1024;
 constexpr int kRowElems = 2048;  // complex values of LDS per block of a row pass (32 KB)
 
-constexpr double kC3 = 0.86602540378443864676;   // sin(2 pi/3)
-constexpr double kR5 = 0.55901699437494742410;   // sqrt(5)/4 = (cos(2 pi/5) - cos(4 pi/5))/2
-constexpr double kS51 = 0.95105651629515357212;  // sin(2 pi/5)
-constexpr double kS52 = 0.58778525229247312917;  // sin(4 pi/5)
-
-// -i a forward, +i a backward
-template <bool Inv>
-__device__ __forceinline__ cd rot(cd a) {
-  return Inv ? cd{-a.y, a.x} : cd{a.y, -a.x};
-}
-__device__ __forceinline__ cd cscale(double s, cd a) { return cd{s * a.x, s * a.y}; }
-
-// x <- the length-R transform of x with W_R = exp(-2 pi i/R) (Inv: its conjugate)
-template <int R, bool Inv>
-__device__ __forceinline__ void dft(cd (&x)[R]) {
-  if constexpr (R == 2) {
-    const cd a = x[0];
-    x[0] = cadd(a, x[1]);
-    x[1] = csub(a, x[1]);
-  } else if constexpr (R == 3) {
-    const cd t = cadd(x[1], x[2]);
-    const cd b = rot<Inv>(cscale(kC3, csub(x[1], x[2])));
-    const cd a = cd{x[0].x - 0.5 * t.x, x[0].y - 0.5 * t.y};
-    x[0] = cadd(x[0], t);
-    x[1] = cadd(a, b);
-    x[2] = csub(a, b);
-  } else if constexpr (R == 4) {
-    const cd a = cadd(x[0], x[2]), b = csub(x[0], x[2]);
-    const cd c = cadd(x[1], x[3]), d = rot<Inv>(csub(x[1], x[3]));
-    x[0] = cadd(a, c);
-    x[1] = cadd(b, d);
-    x[2] = csub(a, c);
-    x[3] = csub(b, d);
-  } else {
-    static_assert(R == 5, "radix 2, 3, 4 or 5");
-    const cd t1 = cadd(x[1], x[4]), t2 = cadd(x[2], x[3]);
-    const cd t3 = csub(x[1], x[4]), t4 = csub(x[2], x[3]);
-    // cos(2 pi/5) + cos(4 pi/5) = -1/2, their difference sqrt(5)/2: in this form a constant input
-    // (t1 = t2 = 2 x0) leaves a1 = a2 = 0 exactly, as the other radices do, so a row or column of
-    // equal values puts no rounding into the wavenumbers whose symbol is cond(A0) times smaller
-    const cd s = cadd(t1, t2), d = cscale(kR5, csub(t1, t2));
-    const cd c = cd{x[0].x - 0.25 * s.x, x[0].y - 0.25 * s.y};
-    const cd a1 = cadd(c, d), a2 = csub(c, d);
-    const cd b1 = rot<Inv>(cd{kS51 * t3.x + kS52 * t4.x, kS51 * t3.y + kS52 * t4.y});
-    const cd b2 = rot<Inv>(cd{kS52 * t3.x - kS51 * t4.x, kS52 * t3.y - kS51 * t4.y});
-    x[0] = cadd(x[0], s);
-    x[1] = cadd(a1, b1);
-    x[2] = cadd(a2, b2);
-    x[3] = csub(a2, b2);
-    x[4] = csub(a1, b1);
-  }
-}
-
 // One stage of nb transforms of length n (transform b at buf + b * stride): groups of g values,
 // radix R.  tw[j * tws] = exp(-2 pi i j/n) for every j < n.
 template <int R, bool Inv>
@@ -309,8 +256,16 @@ __global__ __launch_bounds__(kColThreadsMax) void fftpc_mixed_cols(
   }
 }
 
+int col_threads(const FftPcPlan& p) {
+  const int want = int(p.ny) * p.cols / 4;
+  return std::min(kColThreadsMax, std::max(64, (want + 63) / 64 * 64));
+}
+size_t col_lds(const FftPcPlan& p) { return sizeof(cd) * size_t(p.ny + 1) * size_t(p.cols); }
+
+}  // namespace
+
 // the 3s, the 5s, 4 while two factors of 2 remain, then 2 (see the header: stage order)
-FftStages stages_of(int n) {
+FftStages fftpc_stages_of(int n) {
   FftStages st;
   st.n = n;
   int v = n;
@@ -323,7 +278,7 @@ FftStages stages_of(int n) {
 }
 
 // perm[p]: where the forward transform leaves wavenumber p = k0 + r0 (k1 + r1 (...))
-void digit_reversal(const FftStages& st, int32_t* perm) {
+void fftpc_digit_reversal(const FftStages& st, int32_t* perm) {
   for (int p = 0; p < st.n; ++p) {
     int rem = p, span = st.n, pos = 0;
     for (int t = 0; t < st.ns; ++t) {
@@ -337,7 +292,7 @@ void digit_reversal(const FftStages& st, int32_t* perm) {
 
 // exp(-2 pi i j / n) for every j < n (n even), in long double, rounded once; the roots on the axes
 // exact
-void roots(int64_t n, double* out) {
+void fftpc_roots(int64_t n, double* out) {
   const long double two_pi = 6.283185307179586476925286766559005768L;
   for (int64_t j = 0; j < n; ++j) {
     const long double a = two_pi * static_cast<long double>(j) / static_cast<long double>(n);
@@ -356,14 +311,6 @@ void roots(int64_t n, double* out) {
   }
 }
 
-int col_threads(const FftPcPlan& p) {
-  const int want = int(p.ny) * p.cols / 4;
-  return std::min(kColThreadsMax, std::max(64, (want + 63) / 64 * 64));
-}
-size_t col_lds(const FftPcPlan& p) { return sizeof(cd) * size_t(p.ny + 1) * size_t(p.cols); }
-
-}  // namespace
-
 int fftpc_mixed_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r, double k,
                        double* work) {
   *p = FftPcPlan{};
@@ -374,8 +321,8 @@ int fftpc_mixed_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r,
   p->r = r;
   p->ik = 1.0 / k;
   const int64_t m = nx / 2;
-  p->sx = stages_of(int(m));
-  p->sy = stages_of(int(ny));
+  p->sx = fftpc_stages_of(int(m));
+  p->sy = fftpc_stages_of(int(ny));
   p->rows = int(std::max<int64_t>(1, std::min<int64_t>(ny, kRowElems / m)));
   // 64 KB of LDS per block of the column pass where at least two columns fit in it, two columns
   // otherwise (ny > 2048: up to 128 KB).  The kernel's limit is raised once to the family's
@@ -391,11 +338,11 @@ int fftpc_mixed_create(FftPcPlan* p, int64_t ny, int64_t nx, double h, double r,
   // twx, twy (doubles), then permx, permy (int32)
   const size_t nd = size_t(2 * (nx + ny)), ni = size_t(m + ny);
   std::vector<double> tab(nd + (ni + 1) / 2);
-  roots(nx, tab.data());
-  roots(ny, tab.data() + 2 * nx);
+  fftpc_roots(nx, tab.data());
+  fftpc_roots(ny, tab.data() + 2 * nx);
   int32_t* perm = reinterpret_cast<int32_t*>(tab.data() + nd);
-  digit_reversal(p->sx, perm);
-  digit_reversal(p->sy, perm + m);
+  fftpc_digit_reversal(p->sx, perm);
+  fftpc_digit_reversal(p->sy, perm + m);
   if (hipMalloc(reinterpret_cast<void**>(&p->tables), sizeof(double) * tab.size()) != hipSuccess) {
     p->tables = nullptr;
     (void)hipGetLastError();

@@ -234,6 +234,20 @@ bool shlin_resident_pc_fits(int64_t ny, int64_t nx);
 // exp(-2 pi i j / nx), j < nx/2, then exp(-2 pi i j / ny), j < ny/2 (host, nx + ny doubles)
 void shlin_resident_pc_tables(int64_t ny, int64_t nx, double* out);
 hipError_t shlin_resident_pc_launch(const ShLinResidentPcArgs& P, int64_t batch, hipStream_t s);
+// The same preconditioned CG on grids whose sides are 2^a 3^b 5^c (shlin_resident_pcm.hip): the
+// transforms are wave-local mixed-radix ones.  Serves even sides of that form in [6, 128], at least
+// one of them no power of two (shlin_resident_pc_fits has the others), with ny nx <=
+// kShLinResidentPcMixedMaxPoints and an LDS footprint (shlin_resident_pcm_lds_bytes) within the
+// workgroup's 160 KB.  P.tables: shlin_resident_pcm_tables.
+constexpr int64_t kShLinResidentPcMixedMaxPoints = 9216;
+bool shlin_resident_pcm_fits(int64_t ny, int64_t nx);
+size_t shlin_resident_pcm_lds_bytes(int64_t ny, int64_t nx);
+// all nx roots, all ny roots (fftpc_roots), then as int32 permx (nx/2 entries: the position of
+// wavenumber k in the low half, the wavenumber at position k in the high half) and permy (ny
+// entries: positions)
+size_t shlin_resident_pcm_table_doubles(int64_t ny, int64_t nx);
+void shlin_resident_pcm_tables(int64_t ny, int64_t nx, double* out);
+hipError_t shlin_resident_pcm_launch(const ShLinResidentPcArgs& P, int64_t batch, hipStream_t s);
 // dst = src, streamed in 16-KB chunks per block (the bench's per-box bandwidth probe); n even,
 // 16-B aligned
 hipError_t stream_copy_launch(const double* src, double* dst, int64_t n, hipStream_t s);

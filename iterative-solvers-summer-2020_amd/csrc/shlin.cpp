@@ -43,6 +43,7 @@ ShLinStepper::~ShLinStepper() {
   (void)hipFree(bpc_);
   (void)hipHostFree(bpc_h_);
   (void)hipFree(rtab_);
+  (void)hipFree(rtab_mixed_);
 }
 
 int ShLinStepper::set_precond(int kind) {
@@ -271,12 +272,21 @@ int ShLinStepper::run_batch_pc(const double* U, const double* Uo, double* Unew, 
     return rc;
   }
   // refusals come before anything is launched or allocated
-  if (kind != NK_PC_SPECTRAL || !U || !Uo || !Unew || batch < 1 || batch > 0x7fffffff ||
-      nsteps < 1 || !shlin_resident_pc_fits(ny_, nx_) || fftpc_check(ny_, nx_, h_, r_, k_))
+  const bool mixed = kind == NK_PC_SPECTRAL_MIXED;
+  if ((kind != NK_PC_SPECTRAL && !mixed) || !U || !Uo || !Unew || batch < 1 ||
+      batch > 0x7fffffff || nsteps < 1)
     return NK_EINVAL;
-  if (!rtab_) {
-    std::vector<double> tab(size_t(nx_ + ny_));
-    shlin_resident_pc_tables(ny_, nx_, tab.data());
+  if (mixed ? !shlin_resident_pcm_fits(ny_, nx_) || fftpc_check_mixed(ny_, nx_, h_, r_, k_)
+            : !shlin_resident_pc_fits(ny_, nx_) || fftpc_check(ny_, nx_, h_, r_, k_))
+    return NK_EINVAL;
+  double*& rtab = mixed ? rtab_mixed_ : rtab_;
+  if (!rtab) {
+    std::vector<double> tab(mixed ? shlin_resident_pcm_table_doubles(ny_, nx_)
+                                  : size_t(nx_ + ny_));
+    if (mixed)
+      shlin_resident_pcm_tables(ny_, nx_, tab.data());
+    else
+      shlin_resident_pc_tables(ny_, nx_, tab.data());
     double* d = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * tab.size()) != hipSuccess) {
       (void)hipGetLastError();
@@ -287,7 +297,7 @@ int ShLinStepper::run_batch_pc(const double* U, const double* Uo, double* Unew, 
       (void)hipFree(d);
       return NK_EHIP;
     }
-    rtab_ = d;
+    rtab = d;
   }
   if (const int rc = grow_batch_out(batch)) return rc;
   if (batch > bpc_cap_) {
@@ -306,10 +316,11 @@ int ShLinStepper::run_batch_pc(const double* U, const double* Uo, double* Unew, 
   }
   ShLinResidentPcArgs P;
   resident_args(&P.a, U, Uo, Unew, Uprev, nsteps, r, g);
-  P.tables = rtab_;
+  P.tables = rtab;
   P.ih2 = 1.0 / (h_ * h_);
   P.out = bpc_;
-  hipError_t e1 = shlin_resident_pc_launch(P, batch, E.s);
+  hipError_t e1 = mixed ? shlin_resident_pcm_launch(P, batch, E.s)
+                        : shlin_resident_pc_launch(P, batch, E.s);
   if (e1 == hipSuccess)
     e1 = hipMemcpyAsync(bout_h_, bout_, sizeof(*bout_) * batch, hipMemcpyDeviceToHost, E.s);
   if (e1 == hipSuccess)

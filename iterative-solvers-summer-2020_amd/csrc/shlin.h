@@ -59,8 +59,13 @@ class ShLinStepper {
   // (shlin_resident_pc.hip), for ny, nx powers of two in [8, 128] with ny nx <=
   // kShLinResidentPcMaxPoints and k r < 2.  A member whose own k r_m >= 2 ends with NK_NONFINITE
   // before its first step.  applies, shift (host, may be null): applications of M over the run and
-  // sigma of the last solve, per member.  Any other kind or grid: NK_EINVAL, nothing launched or
-  // allocated.  The first spectral call allocates the twiddle table (nx + ny doubles).
+  // sigma of the last solve, per member.  NK_PC_SPECTRAL_MIXED: the same solve with wave-local
+  // mixed-radix transforms (shlin_resident_pcm.hip), for even sides 2^a 3^b 5^c in [6, 128], at
+  // least one of them no power of two (a grid of two powers of two belongs to NK_PC_SPECTRAL and is
+  // refused under this kind), ny nx <= kShLinResidentPcMixedMaxPoints and an LDS footprint that
+  // fits (shlin_resident_pcm_fits).  Any other kind or grid: NK_EINVAL, nothing launched or
+  // allocated.  The first call of a kind allocates its table (nx + ny doubles; mixed:
+  // shlin_resident_pcm_table_doubles).
   int run_batch_pc(const double* U, const double* Uo, double* Unew, double* Uprev, int64_t batch,
                    int64_t nsteps, const double* r, const double* g, int kind, int64_t* iters,
                    int64_t* steps_done, double* relres, int32_t* status, int64_t* applies,
@@ -93,6 +98,7 @@ class ShLinStepper {
   ShLinResidentPcOut* bpc_h_ = nullptr;
   int64_t bpc_cap_ = 0;
   double* rtab_ = nullptr;
+  double* rtab_mixed_ = nullptr;  // the mixed kernel's: all roots and the permutations
   int grow_batch_out(int64_t batch);
   void resident_args(ShLinResidentArgs* A, const double* U, const double* Uo, double* Unew,
                      double* Uprev, int64_t nsteps, const double* r, const double* g) const;

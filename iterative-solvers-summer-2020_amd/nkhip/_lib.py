@@ -183,6 +183,7 @@ SIGNATURES = [
     ("nk_shlin_run_batch_pc", C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I32, _P, _P, _P,
                                         _P, _P, _P]),
     ("nk_shlin_resident_precond_max_points", C.c_int64, []),
+    ("nk_shlin_resident_precond_mixed_max_points", C.c_int64, []),
     ("nk_shlin_set_precond", C.c_int, [_P, _I32]),
     ("nk_shlin_precond_applies", C.c_int64, [_P]),
     ("nk_shlin_precond_shift", C.c_double, [_P]),

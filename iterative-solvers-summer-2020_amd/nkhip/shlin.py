@@ -18,7 +18,9 @@ the unpreconditioned one.
 ``run_batch`` / ``step_batch`` serve small grids (ny*N <= ``resident_max_points``) and ensembles of
 them: one workgroup per state runs whole steps on chip, in one launch for the batch.  Their own
 ``precond="spectral"`` applies the same preconditioner inside the resident workgroup (N and ny
-powers of two in [8, 128], ny*N <= ``resident_precond_max_points``).
+powers of two in [8, 128], ny*N <= ``resident_precond_max_points``), ``precond="spectral-mixed"``
+on even sides 2^a 3^b 5^c in [6, 128] that are not both powers of two (ny*N <=
+``resident_precond_mixed_max_points``).
 """
 from __future__ import annotations
 
@@ -115,6 +117,9 @@ class SHLinearised:
     #: the cap of ``run_batch(..., precond="spectral")`` in grid points (host only; 128 x 64)
     resident_precond_max_points = int(lib.nk_shlin_resident_precond_max_points())
 
+    #: the cap of ``run_batch(..., precond="spectral-mixed")`` in grid points (host only; 96 x 96)
+    resident_precond_mixed_max_points = int(lib.nk_shlin_resident_precond_mixed_max_points())
+
     def run_batch(self, U, Uo=None, nsteps=1, r=None, g=None, precond=None):
         """``nsteps`` steps of B independent states in one launch, one workgroup per state with
         the whole CG solve on chip (csrc/shlin_resident.hip).  ``U``: (B, ny*N), or one state
@@ -131,13 +136,19 @@ class SHLinearised:
         mesh is refined.  It needs N and ny powers of two in [8, 128], ny*N <=
         ``resident_precond_max_points`` and k r < 2 (anything else raises and leaves the stepper
         usable); a member whose own k r >= 2 stops as a non-finite one does.
+        ``"spectral-mixed"`` is the same solve (M, sigma, stopping rule, guards, counters) with
+        wave-local mixed-radix transforms (csrc/shlin_resident_pcm.hip), for N and ny even, of the
+        form 2^a 3^b 5^c, in [6, 128] and not both powers of two, ny*N <=
+        ``resident_precond_mixed_max_points`` (96 x 96, 128 x 72 and 72 x 128 fit; a grid whose
+        plane, spectrum and tables exceed a workgroup's LDS raises).  A grid whose sides are both
+        powers of two raises under this name: ``"spectral"`` serves it.
 
         A member's bits depend on its own inputs alone.  A member that fails a step stops with its
         last accepted pair; ``NoConvergence`` (carrying ``U_new``) or the non-finite error is
         raised after ``last_batch`` is filled; ``last_batch_state`` then holds ``(U_new, U_prev)``,
         the other members' results among them."""
-        if precond not in (None, "none", "spectral"):
-            raise ValueError(f"precond={precond!r}: None, 'none' or 'spectral'")
+        if precond not in (None, "none", "spectral", "spectral-mixed"):
+            raise ValueError(f"precond={precond!r}: None, 'none', 'spectral' or 'spectral-mixed'")
         n = self.ny * self.N
         U = torch.as_tensor(U).to(device="cuda", dtype=torch.float64).contiguous()
         if U.numel() == 0 or U.numel() % n or (U.dim() > 1 and U.shape[0] * n != U.numel()):
@@ -167,9 +178,10 @@ class SHLinearised:
                "status": torch.zeros(B, dtype=torch.int32),
                "precond": torch.zeros(B, dtype=torch.int64),
                "shift": torch.zeros(B, dtype=torch.float64)}
-        if precond == "spectral":
+        if precond in ("spectral", "spectral-mixed"):
+            kind = _lib.NK_PC_SPECTRAL if precond == "spectral" else _lib.NK_PC_SPECTRAL_MIXED
             rc = lib.nk_shlin_run_batch_pc(self._h, ptr(U), ptr(Uo), ptr(new), ptr(prev), B,
-                                           int(nsteps), ptr(r), ptr(g), _lib.NK_PC_SPECTRAL,
+                                           int(nsteps), ptr(r), ptr(g), kind,
                                            ptr(res["iters"]), ptr(res["steps"]),
                                            ptr(res["relres"]), ptr(res["status"]),
                                            ptr(res["precond"]), ptr(res["shift"]))

@@ -16,6 +16,10 @@ iteration minus the plain leg's (one application per iteration).  Every leg is w
 launches it times; host clock around calls that end in a device synchronise; best of --reps.
 
     python scripts/shlin_resident_precond_probe.py --ny 64 --nx 64 --h 0.0625 [--out profiles/...md]
+    python scripts/shlin_resident_precond_probe.py --ny 96 --nx 96 --kind spectral-mixed
+
+--kind names the preconditioner of the spectral and `step` legs: "spectral" (sides that are powers
+of two) or "spectral-mixed" (sides 2^a 3^b 5^c, csrc/shlin_resident_pcm.hip).
 
 Run each grid as a command of its own under a time limit and chain them with &&, so that a failed
 leg starts nothing more on the GPU.
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--ny", type=int, default=64)
     ap.add_argument("--nx", type=int, default=64)
     ap.add_argument("--h", type=float, default=0.0625)
+    ap.add_argument("--kind", default="spectral", choices=["spectral", "spectral-mixed"])
     ap.add_argument("--batches", default="1,256")
     ap.add_argument("--steps", type=int, default=20, help="steps of the shorter spectral launch")
     ap.add_argument("--plain-steps", type=int, default=2, help="the same for the plain leg")
@@ -54,7 +59,7 @@ def main():
                                                                             ny * nx)), device="cuda")
     kw = dict(N=nx, ny=ny, d=h * nx, k=k, r=r, g=g)
     s = nkhip.SHLinearised(maxiter=20000, **kw)
-    m = nkhip.SHLinearised(precond="spectral", **kw)
+    m = nkhip.SHLinearised(precond=args.kind, **kw)
     rows = []
 
     def timed(fn):
@@ -92,13 +97,13 @@ def main():
 
     try:
         for B in batches:
-            pc = one_launch("`run_batch(precond=\"spectral\")`", B, args.steps, "spectral")
+            pc = one_launch(f"`run_batch(precond=\"{args.kind}\")`", B, args.steps, args.kind)
             cg = one_launch("`run_batch`, plain", B, args.plain_steps, None)
             rows.append(f"| one application of M (difference of the two) | {B} | | | | | | "
                         f"{1e6 * (pc - cg):.2f} |")
             print(rows[-1], flush=True)
         dt, its = timed(loop_step)
-        rows.append(f"| `step` loop, `precond=\"spectral\"` | 1 | {args.loop} | {args.loop / dt:.1f} | "
+        rows.append(f"| `step` loop, `precond=\"{args.kind}\"` | 1 | {args.loop} | {args.loop / dt:.1f} | "
                     f"{args.loop / dt:.1f} | {its / args.loop:.1f} | {1e6 * dt / args.loop:.1f} | "
                     f"{1e6 * dt / its:.2f} |")
         print(rows[-1], flush=True)
@@ -106,7 +111,7 @@ def main():
         s.close()
         m.close()
     text = "\n".join([f"## shlin_resident_precond_probe: {ny} x {nx}, h = {h}, k = {k}, r = {r}, "
-                      f"g = {g}", "",
+                      f"g = {g}, {args.kind}", "",
                       "| leg | B | steps | steps/s per member | steps/s in total | "
                       "CG iterations/step (member 0) | us per step | us per CG iteration |",
                       "|---|---|---|---|---|---|---|---|"] + rows) + "\n"
