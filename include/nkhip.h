@@ -365,6 +365,38 @@ int64_t nk_sh_workspace_bytes(nk_sh* s);
 int nk_sh_set_precond(nk_sh* s, int32_t kind);
 /* Applications of M in the last nk_sh_step (0 without a preconditioner; -1: s == NULL). */
 int64_t nk_sh_precond_applies(nk_sh* s);
+/* `nsteps` implicit steps of `batch` independent states in ONE launch, for small grids and
+ * ensembles of them: one workgroup per state runs whole steps on chip, state in registers and one
+ * framed plane in LDS.  The method is Newton-CG, not nk_sh_step's Newton-LGMRES: the Jacobian is
+ * the analytic one, k J(u) = I + k (1.5 u^2 - g u) - L k/2, symmetric and positive definite
+ * whenever k (g^2/6 + r/2) < 1, and the Newton correction is solved by conjugate gradients.  The
+ * outer loop is nk_sh_step's: stop on max|F| <= f_tol, the forcing terms, the Armijo line search
+ * (or full steps), Newton's maxiter -- f_tol, maxiter and line_search are the stepper's options;
+ * f_rtol, x_tol and x_rtol must be unset.  It reaches the same root to f_tol's scale; its
+ * iteration counts are not scipy's.  An inner solve ends at its tolerance or after inner_maxiter
+ * iterations, whichever comes first; reaching the cap is no failure.
+ * kind NK_PC_NONE: plain CG, for grids with both sides >= 5 and ny nx <=
+ * nk_shlin_resident_max_points().  NK_PC_SPECTRAL: CG preconditioned with
+ *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean k (1.5 u^2 - g u), 0)  per Newton iteration,
+ * applied inside the workgroup, for nx and ny powers of two in [8, 128] with ny nx <=
+ * nk_shlin_resident_precond_max_points() and k r < 2.  nk_sh_set_precond and the stepper's
+ * jvp_mode have no effect here.  One GPU: a stepper with a communicator is refused.
+ * States are `batch` contiguous rows of ny nx doubles; Unew_dev may be U_dev.  r_dev, g_dev:
+ * `batch` doubles each, per-member r and g, or NULL for the stepper's own.  A member's result
+ * depends on its own inputs alone.  A member with k (g^2/6 + r/2) >= 1, a non-finite r or g, or
+ * (NK_PC_SPECTRAL) k r >= 2 ends with NK_NONFINITE before its first step, its output its input.  A
+ * member that meets non-finite values or p.Ap <= 0 (NK_NONFINITE), or Newton's maxiter
+ * (NK_NO_CONVERGENCE), stops with the last state it completed a step to; the others go on.  Host
+ * arrays of `batch` entries, any of them NULL: Newton iterations, CG iterations and steps
+ * completed over the run, max|F| at the last iterate, status, applications of M over the run and
+ * sigma of the last solve.  Returns the worst member status (NK_NONFINITE over NK_NO_CONVERGENCE
+ * over NK_OK); NK_EINVAL, with nothing launched or allocated and the stepper unchanged, for any
+ * other kind or grid, k <= 0, batch, nsteps or inner_maxiter < 1.  Synchronises the stepper's
+ * stream. */
+int nk_sh_run_batch(nk_sh* s, const double* U_dev, double* Unew_dev, int64_t batch, int64_t nsteps,
+                    const double* r_dev, const double* g_dev, int32_t kind, int64_t inner_maxiter,
+                    int64_t* nit, int64_t* iters, int64_t* steps_done, double* fnorm,
+                    int32_t* status, int64_t* applies, double* shift);
 
 /* ---------------- generic drop-in: newton_krylov(F, xin) over a device residual ---------------- */
 /* F(ctx, x_dev, f_dev, n) evaluates the residual on device buffers and returns 0 on success.

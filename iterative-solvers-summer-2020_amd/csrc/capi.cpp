@@ -847,6 +847,15 @@ int nk_sh_set_precond(nk_sh* s, int32_t kind) {
 
 int64_t nk_sh_precond_applies(nk_sh* s) { return s ? s->NK->precond_applies() : -1; }
 
+int nk_sh_run_batch(nk_sh* s, const double* U, double* Unew, int64_t batch, int64_t nsteps,
+                    const double* r, const double* g, int32_t kind, int64_t inner_maxiter,
+                    int64_t* nit, int64_t* iters, int64_t* steps_done, double* fnorm,
+                    int32_t* status, int64_t* applies, double* shift) {
+  if (!s) return NK_EINVAL;
+  return s->P->run_batch(U, Unew, batch, nsteps, r, g, kind, s->opts, inner_maxiter, nit, iters,
+                         steps_done, fnorm, status, applies, shift);
+}
+
 int nk_sh_precond_apply(const double* v, double* z, int64_t ny, int64_t nx, double h, double r,
                         double k, void* stream) {
   return nk_sh_precond_apply_kind(v, z, ny, nx, h, r, k, NK_PC_SPECTRAL, stream);

@@ -248,6 +248,36 @@ size_t shlin_resident_pcm_lds_bytes(int64_t ny, int64_t nx);
 size_t shlin_resident_pcm_table_doubles(int64_t ny, int64_t nx);
 void shlin_resident_pcm_tables(int64_t ny, int64_t nx, double* out);
 hipError_t shlin_resident_pcm_launch(const ShLinResidentPcArgs& P, int64_t batch, hipStream_t s);
+// Whole implicit Crank-Nicolson steps of small grids on chip, one workgroup per state of a batch
+// (sh_resident.hip): Newton's method with the analytic Jacobian, the forcing terms and the Armijo
+// line search of NewtonKrylov::solve, and CG on k J = I + D - L k/2 inside (plain, or with the
+// spectral preconditioner of shlin_resident_pc.hip when `tables` is set).  The grids and caps are
+// the semi-implicit kernels': shlin_resident_fits, and shlin_resident_pc_fits with tables.
+struct ShResidentOut {
+  int64_t nit;      // Newton iterations over the run
+  int64_t iters;    // CG iterations over the run
+  int64_t steps;    // steps completed
+  int64_t applies;  // applications of M over the run
+  double fnorm;     // max|F| at the last Newton iterate
+  double shift;     // sigma of the last solve
+  int64_t status;   // NK_OK, or what stopped the member (NK_NO_CONVERGENCE, NK_NONFINITE)
+};
+struct ShResidentArgs {
+  int ny = 0, nx = 0;
+  const double* U = nullptr;  // batch rows of ny nx doubles
+  double* Unew = nullptr;     // the last accepted state of every member (may be U)
+  const double* r = nullptr;  // per member, or null: r0
+  const double* g = nullptr;  // per member, or null: g0
+  double r0 = 0.0, g0 = 0.0;
+  double cbase = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;  // sh_coef's, the centre as c0 - r + 1
+  double k = 0.0, f_tol = 0.0;
+  int64_t maxiter = 0, inner_maxiter = 0, nsteps = 0;  // Newton's cap, CG's cap per solve
+  int line_search = 1;                                 // 1: Armijo, 0: full steps
+  const double* tables = nullptr;  // shlin_resident_pc_tables, or null: plain CG
+  double ih2 = 0.0;                // 1 / h^2
+  ShResidentOut* out = nullptr;    // batch entries
+};
+hipError_t sh_resident_launch(const ShResidentArgs& A, int64_t batch, hipStream_t s);
 // dst = src, streamed in 16-KB chunks per block (the bench's per-box bandwidth probe); n even,
 // 16-B aligned
 hipError_t stream_copy_launch(const double* src, double* dst, int64_t n, hipStream_t s);

@@ -94,6 +94,9 @@ SHProblem::~SHProblem() {
   if (B_) hipFree(B_);
   if (hx_) hipFree(hx_);
   if (mb_) hipFree(mb_);
+  if (bout_) hipFree(bout_);
+  if (bout_h_) hipHostFree(bout_h_);
+  if (rtab_) hipFree(rtab_);
   if (ev_in_) hipEventDestroy(ev_in_);
   if (ev_out_) hipEventDestroy(ev_out_);
   if (side_) hipStreamDestroy(side_);
@@ -602,6 +605,94 @@ int SHProblem::precond(const double* in, double* out) {
   if (!pc_on_) return NK_EINVAL;
   return E_.launch(K_PRECOND, fftpc_bytes(pc_),
                    [&] { return fftpc_apply(pc_, in, out, E_.s); });
+}
+
+int SHProblem::run_batch(const double* U, double* Unew, int64_t batch, int64_t nsteps,
+                         const double* r, const double* g, int kind, const nk_opts& o,
+                         int64_t inner_maxiter, int64_t* nit, int64_t* iters, int64_t* steps_done,
+                         double* fnorm, int32_t* status, int64_t* applies, double* shift) {
+  if (status_) return status_;
+  // refusals come before anything is launched or allocated
+  const bool pc = kind == NK_PC_SPECTRAL;
+  if ((kind != NK_PC_NONE && !pc) || !U || !Unew || batch < 1 || batch > 0x7fffffff ||
+      nsteps < 1 || inner_maxiter < 1 || dist() || ny_g_ != ny_ || !(c_.k > 0.0) ||
+      !std::isnan(o.f_rtol) || !std::isnan(o.x_tol) || !std::isnan(o.x_rtol))
+    return NK_EINVAL;
+  if (pc ? !shlin_resident_pc_fits(ny_, nx_) || fftpc_check(ny_, nx_, h_, r_, c_.k)
+         : !shlin_resident_fits(ny_, nx_))
+    return NK_EINVAL;
+  if (pc && !rtab_) {
+    std::vector<double> tab(size_t(nx_ + ny_));
+    shlin_resident_pc_tables(ny_, nx_, tab.data());
+    double* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * tab.size()) != hipSuccess) {
+      (void)hipGetLastError();
+      return NK_ENOMEM;
+    }
+    if (hipMemcpy(d, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) !=
+        hipSuccess) {
+      (void)hipFree(d);
+      return NK_EHIP;
+    }
+    rtab_ = d;
+  }
+  if (batch > bout_cap_) {  // the last call synchronised: nothing reads the old entries
+    ShResidentOut *d = nullptr, *h = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(*d) * batch) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(*h) * batch) != hipSuccess) {
+      (void)hipFree(d);
+      (void)hipGetLastError();
+      return NK_ENOMEM;
+    }
+    (void)hipFree(bout_);
+    (void)hipHostFree(bout_h_);
+    bout_ = d;
+    bout_h_ = h;
+    bout_cap_ = batch;
+  }
+  ShResidentArgs A;
+  A.ny = int(ny_);
+  A.nx = int(nx_);
+  A.U = U;
+  A.Unew = Unew;
+  A.r = r;
+  A.g = g;
+  A.r0 = r_;
+  A.g0 = c_.g;
+  const double e = 1.0 / (h_ * h_);
+  A.cbase = -20.0 * e * e + 8.0 * e;  // sh_coef's centre is cbase + r - 1
+  A.c1 = c_.c1;
+  A.c2 = c_.c2;
+  A.c3 = c_.c3;
+  A.k = c_.k;
+  // the defaults of NewtonKrylov::solve
+  A.f_tol = std::isnan(o.f_tol) ? std::pow(2.220446049250313e-16, 1.0 / 3.0) : o.f_tol;
+  A.maxiter = o.maxiter > 0 ? o.maxiter : 100 * (n_global() + 1);
+  A.inner_maxiter = inner_maxiter;
+  A.nsteps = nsteps;
+  A.line_search = o.line_search ? 1 : 0;
+  A.tables = pc ? rtab_ : nullptr;
+  A.ih2 = e;
+  A.out = bout_;
+  hipError_t e1 = sh_resident_launch(A, batch, E_.s);
+  if (e1 == hipSuccess)
+    e1 = hipMemcpyAsync(bout_h_, bout_, sizeof(*bout_) * batch, hipMemcpyDeviceToHost, E_.s);
+  if (e1 != hipSuccess) return NK_EHIP;
+  if (const int rc = E_.sync()) return rc;
+  int worst = NK_OK;
+  for (int64_t b = 0; b < batch; ++b) {
+    const ShResidentOut& m = bout_h_[b];
+    if (nit) nit[b] = m.nit;
+    if (iters) iters[b] = m.iters;
+    if (steps_done) steps_done[b] = m.steps;
+    if (fnorm) fnorm[b] = m.fnorm;
+    if (status) status[b] = int32_t(m.status);
+    if (applies) applies[b] = m.applies;
+    if (shift) shift[b] = m.shift;
+    if (m.status == NK_NONFINITE || (m.status == NK_NO_CONVERGENCE && worst == NK_OK))
+      worst = int(m.status);
+  }
+  return worst;
 }
 
 void SHProblem::void_fused_steps(int count) {

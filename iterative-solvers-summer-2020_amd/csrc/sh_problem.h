@@ -49,6 +49,21 @@ class SHProblem final : public Problem {
   int set_precond(int kind);
   bool has_precond() const override { return pc_on_; }
   int precond(const double* in, double* out) override;
+  // `nsteps` implicit steps of `batch` independent states (contiguous rows of ny nx doubles) in one
+  // launch of sh_resident.hip: one workgroup per state runs Newton-CG on chip with the analytic
+  // Jacobian, whatever jvp_mode and set_precond say.  kind: NK_PC_NONE (plain CG; sides >= 5,
+  // ny nx <= kShLinResidentMaxPoints) or NK_PC_SPECTRAL (ny, nx powers of two in [8, 128],
+  // ny nx <= kShLinResidentPcMaxPoints, k r < 2).  o gives f_tol, Newton's maxiter and line_search;
+  // the other tolerances must be unset.  r, g: per-member device arrays, or null for the
+  // problem's values.  A member refused (k (g^2/6 + r/2) >= 1; spectral: k r >= 2) or stopped
+  // (NK_NONFINITE, NK_NO_CONVERGENCE) leaves its last accepted state in Unew; the others go on.
+  // Host results per member (any may be null).  Returns the worst member status; NK_EINVAL, with
+  // nothing launched or allocated, for a slab of a distributed grid, any other kind or grid,
+  // k <= 0, batch, nsteps or inner_maxiter < 1.  Synchronises.
+  int run_batch(const double* U, double* Unew, int64_t batch, int64_t nsteps, const double* r,
+                const double* g, int kind, const nk_opts& o, int64_t inner_maxiter, int64_t* nit,
+                int64_t* iters, int64_t* steps_done, double* fnorm, int32_t* status,
+                int64_t* applies, double* shift);
 
  private:
   // any communicator (also a world of one: its halo is the periodic wrap through RCCL)
@@ -95,6 +110,12 @@ class SHProblem final : public Problem {
   double h_ = 0.0, r_ = 0.0;  // the grid spacing and r the coefficients were built from
   FftPcPlan pc_{};            // spectral preconditioner (tables != nullptr once built)
   bool pc_on_ = false;
+  // run_batch's per-member results (device entries and their pinned host copy, grown on demand)
+  // and the resident kernel's twiddle table
+  ShResidentOut* bout_ = nullptr;
+  ShResidentOut* bout_h_ = nullptr;
+  int64_t bout_cap_ = 0;
+  double* rtab_ = nullptr;
 };
 
 // newton_krylov(F, xin) for an arbitrary device residual (droplet.py:383, PMA2_nk.py:100, ...):

@@ -1,5 +1,6 @@
-// Device pieces the two resident semi-implicit SH kernels share (shlin_resident.hip: plain CG;
-// shlin_resident_pc.hip: CG with the spectral preconditioner on chip): the fixed-order block sums,
+// Device pieces the resident SH kernels share (shlin_resident.hip: the semi-implicit step with plain
+// CG; shlin_resident_pc.hip, shlin_resident_pcm.hip: with the spectral preconditioner on chip;
+// sh_resident.hip: the implicit step by Newton-CG): the fixed-order block sums,
 // the point code of the framed LDS plane, and the 13-point stencil on it.
 #pragma once
 

@@ -154,6 +154,8 @@ SIGNATURES = [
     ("nk_sh_workspace_bytes", C.c_int64, [_P]),
     ("nk_sh_set_precond", C.c_int, [_P, _I32]),
     ("nk_sh_precond_applies", C.c_int64, [_P]),
+    ("nk_sh_run_batch", C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _I32, _I64, _P, _P, _P, _P, _P,
+                                  _P, _P]),
     ("nk_solve_workspace_bytes", C.c_int64, [_I64, C.POINTER(nk_opts)]),
     ("nk_solve", C.c_int, [RESIDUAL_FN, _P, _P, _P, _I64, C.POINTER(nk_opts),
                            C.POINTER(nk_stats), _P, _P, _I64]),

@@ -12,6 +12,10 @@ the C++ twin ``cpp_work/.../main.cpp``) is a module-level loop:
 constants :15-29) and ``step(U)`` is the loop body: hand in a 2-D grid state, get the next
 implicit time step.  The whole Newton-Krylov solve runs on the GPU (nk_sh_step): the residual,
 the finite-difference JVP and the Arnoldi BLAS-1 work are HIP kernels, the host keeps scalars.
+
+``run_batch`` / ``step_batch`` serve small grids (ny*N <= ``resident_max_points``) and ensembles of
+them: one workgroup per state runs whole implicit steps on chip, Newton-CG with the analytic
+Jacobian, in one launch for the batch (csrc/sh_resident.hip).
 """
 from __future__ import annotations
 
@@ -55,6 +59,8 @@ class SwiftHohenberg:
                                self.k, self.g, C.byref(self.opts),
                                comm.handle if comm is not None else None, s), "nk_sh_create")
         self.last_stats = None
+        self.last_batch = None  # per-member results of the last run_batch
+        self.last_batch_state = None  # its U_new: the survivors' states when it raised
         self.inner_M = None
         if inner_M is not None:
             try:
@@ -154,6 +160,107 @@ class SwiftHohenberg:
             self.step(a, out=b)
             a, b = b, a
         return a
+
+    # ----------------------------------------------------------------------------- small grids
+    #: the cap of ``run_batch`` in grid points (host only; 96 x 96)
+    resident_max_points = int(lib.nk_shlin_resident_max_points())
+
+    #: the cap of ``run_batch(..., precond="spectral")`` in grid points (host only; 128 x 64)
+    resident_precond_max_points = int(lib.nk_shlin_resident_precond_max_points())
+
+    def run_batch(self, U, nsteps=1, r=None, g=None, precond=None, inner_maxiter=1000):
+        """``nsteps`` implicit steps of B independent states in one launch, one workgroup per state
+        with whole steps on chip (csrc/sh_resident.hip): for small grids, where ``step`` is bound
+        by launch and read-back latency, and for ensembles and sweeps in ``r`` and ``g`` of them.
+
+        The method is Newton-CG with the analytic Jacobian, not ``step``'s LGMRES on a difference
+        quotient: k J = I + k (1.5 u^2 - g u) - L k/2 is symmetric positive definite whenever
+        k (g^2/6 + r/2) < 1, so each Newton correction is a conjugate-gradient solve.  The outer
+        loop is ``step``'s (the stop on max|F| <= ``f_tol``, the forcing terms, the Armijo search or
+        ``line_search=None``, Newton's ``maxiter``: the stepper's options).  It reaches the same
+        root to ``f_tol``'s scale; its iteration counts are not SciPy's.  An inner solve ends at
+        its tolerance or after ``inner_maxiter`` iterations; reaching the cap is no failure.
+
+        ``U``: (B, ny*N), or one state (B = 1).  ``r``, ``g``: B values each for a per-member
+        sweep, or None for the stepper's own.  Returns ``U_new`` as (B, ny*N) and fills
+        ``last_batch`` (CPU tensors ``steps``, ``nit``, ``iters``, ``fnorm``, ``status``, and
+        ``precond`` / ``shift``: applications of M over the run and sigma of the last solve,
+        zeros on the plain path) and ``last_batch_state`` (``U_new``).
+
+        ``precond``: ``None`` / ``"none"`` is plain CG, for sides >= 5 and ny*N <=
+        ``resident_max_points``.  ``"spectral"`` preconditions CG with
+        M = ((1 + sigma) I - L k/2)^-1, sigma = max(mean k (1.5 u^2 - g u), 0), applied inside the
+        workgroup: the iteration count no longer grows as the mesh is refined.  It needs N and ny
+        powers of two in [8, 128], ny*N <= ``resident_precond_max_points`` and k r < 2.
+        ``set_precond`` / ``inner_M`` and ``jvp`` have no effect here.  Anything else
+        (``"spectral-mixed"``, another grid, a stepper with ``f_rtol``, ``x_tol`` or ``x_rtol``
+        set, with a communicator or a slab of a larger grid) raises ``ValueError`` and leaves the
+        stepper usable.
+
+        A member's bits depend on its own inputs alone.  A member with k (g^2/6 + r/2) >= 1 (or,
+        under ``"spectral"``, k r >= 2) is refused as a non-finite one is; a member that fails a
+        step stops with the last state it completed a step to.  ``NoConvergence`` (carrying
+        ``U_new``) or the non-finite error is raised after ``last_batch`` and ``last_batch_state``
+        are filled, the other members' results among them."""
+        if precond not in (None, "none", "spectral"):
+            raise ValueError(f"precond={precond!r}: None, 'none' or 'spectral'")
+        if self.comm is not None or self.ny_local != self.ny:
+            raise ValueError("run_batch serves one GPU: no communicator, ny_local == ny")
+        o = self.opts
+        if not (math.isnan(o.f_rtol) and math.isnan(o.x_tol) and math.isnan(o.x_rtol)):
+            raise ValueError("run_batch stops on f_tol alone: f_rtol, x_tol and x_rtol must be unset")
+        ny, nx, n = self.ny, self.nx, self.ny * self.nx
+        if precond == "spectral":
+            side = lambda v: 8 <= v <= 128 and v & (v - 1) == 0  # noqa: E731
+            if not (side(ny) and side(nx) and n <= self.resident_precond_max_points):
+                raise ValueError(f"precond='spectral': N and ny powers of two in [8, 128] with ny*N "
+                                 f"<= {self.resident_precond_max_points}, got {ny} x {nx}")
+            if not self.k * self.r < 2:
+                raise ValueError("precond='spectral' needs k r < 2")
+        elif min(ny, nx) < 5 or n > self.resident_max_points:
+            raise ValueError(f"run_batch: sides >= 5 and ny*N <= {self.resident_max_points}, "
+                             f"got {ny} x {nx}")
+        if not self.k > 0 or int(nsteps) < 1 or int(inner_maxiter) < 1:
+            raise ValueError("run_batch needs k > 0, nsteps >= 1 and inner_maxiter >= 1")
+        U = torch.as_tensor(U).to(device="cuda", dtype=torch.float64).contiguous()
+        if U.numel() == 0 or U.numel() % n or (U.dim() > 1 and U.shape[0] * n != U.numel()):
+            raise ValueError(f"expected (B, {n}) values with B >= 1, got {tuple(U.shape)}")
+        U = U.reshape(-1, n)
+        B = U.shape[0]
+
+        def member(v, name):
+            if v is None:
+                return None
+            v = torch.as_tensor(v).to(device="cuda", dtype=torch.float64).contiguous().reshape(-1)
+            if v.numel() != B:
+                raise ValueError(f"{name}: expected {B} values, got {v.numel()}")
+            return v
+
+        r, g = member(r, "r"), member(g, "g")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        new = torch.empty_like(U)
+        i64 = lambda: torch.zeros(B, dtype=torch.int64)  # noqa: E731
+        res = {"steps": i64(), "nit": i64(), "iters": i64(),
+               "fnorm": torch.zeros(B, dtype=torch.float64),
+               "status": torch.zeros(B, dtype=torch.int32), "precond": i64(),
+               "shift": torch.zeros(B, dtype=torch.float64)}
+        cur = torch.cuda.current_stream(U.device)
+        mine = self._stream if self._stream is not None else cur
+        if mine != cur:
+            mine.wait_stream(cur)
+        kind = _lib.NK_PC_SPECTRAL if precond == "spectral" else _lib.NK_PC_NONE
+        rc = lib.nk_sh_run_batch(self._h, ptr(U), ptr(new), B, int(nsteps), ptr(r), ptr(g), kind,
+                                 int(inner_maxiter), ptr(res["nit"]), ptr(res["iters"]),
+                                 ptr(res["steps"]), ptr(res["fnorm"]), ptr(res["status"]),
+                                 ptr(res["precond"]), ptr(res["shift"]))
+        check(min(rc, 0), "nk_sh_run_batch")
+        self.last_batch, self.last_batch_state = res, new
+        raise_for_status(rc, new)
+        return new
+
+    def step_batch(self, U, r=None, g=None, precond=None, inner_maxiter=1000):
+        """One step of every member: ``run_batch(U, 1, r, g, precond, inner_maxiter)``."""
+        return self.run_batch(U, 1, r, g, precond, inner_maxiter)
 
     # ----------------------------------------------------------------------------- operators
     def L(self, v):
