@@ -379,13 +379,17 @@ int64_t nk_sh_precond_applies(nk_sh* s);
  * nk_shlin_resident_max_points().  NK_PC_SPECTRAL: CG preconditioned with
  *   M = ((1 + sigma) I - L k/2)^-1,  sigma = max(mean k (1.5 u^2 - g u), 0)  per Newton iteration,
  * applied inside the workgroup, for nx and ny powers of two in [8, 128] with ny nx <=
- * nk_shlin_resident_precond_max_points() and k r < 2.  nk_sh_set_precond and the stepper's
+ * nk_shlin_resident_precond_max_points() and k r < 2.  NK_PC_SPECTRAL_MIXED: the same solve with
+ * wave-local mixed-radix transforms, for nx and ny even, of the form 2^a 3^b 5^c, in [6, 128] and
+ * not both powers of two (NK_PC_SPECTRAL serves those), with ny nx <=
+ * nk_shlin_resident_precond_mixed_max_points(), a plane, spectrum and tables within a workgroup's
+ * LDS (96 x 96, 128 x 72 and 72 x 128 fit) and k r < 2.  nk_sh_set_precond and the stepper's
  * jvp_mode have no effect here.  One GPU: a stepper with a communicator is refused.
  * States are `batch` contiguous rows of ny nx doubles; Unew_dev may be U_dev.  r_dev, g_dev:
  * `batch` doubles each, per-member r and g, or NULL for the stepper's own.  A member's result
  * depends on its own inputs alone.  A member with k (g^2/6 + r/2) >= 1, a non-finite r or g, or
- * (NK_PC_SPECTRAL) k r >= 2 ends with NK_NONFINITE before its first step, its output its input.  A
- * member that meets non-finite values or p.Ap <= 0 (NK_NONFINITE), or Newton's maxiter
+ * (either preconditioned kind) k r >= 2 ends with NK_NONFINITE before its first step, its output
+ * its input.  A member that meets non-finite values or p.Ap <= 0 (NK_NONFINITE), or Newton's maxiter
  * (NK_NO_CONVERGENCE), stops with the last state it completed a step to; the others go on.  Host
  * arrays of `batch` entries, any of them NULL: Newton iterations, CG iterations and steps
  * completed over the run, max|F| at the last iterate, status, applications of M over the run and

@@ -278,6 +278,10 @@ struct ShResidentArgs {
   ShResidentOut* out = nullptr;    // batch entries
 };
 hipError_t sh_resident_launch(const ShResidentArgs& A, int64_t batch, hipStream_t s);
+// The same steps, preconditioned, on the grids of shlin_resident_pcm_fits (sh_resident_pcm.hip):
+// the Newton-CG of sh_resident.hip around the mixed-radix transforms of shlin_resident_pcm.hip.
+// A.tables: shlin_resident_pcm_tables (not null).
+hipError_t sh_resident_pcm_launch(const ShResidentArgs& A, int64_t batch, hipStream_t s);
 // dst = src, streamed in 16-KB chunks per block (the bench's per-box bandwidth probe); n even,
 // 16-B aligned
 hipError_t stream_copy_launch(const double* src, double* dst, int64_t n, hipStream_t s);

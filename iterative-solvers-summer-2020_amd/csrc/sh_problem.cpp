@@ -97,6 +97,7 @@ SHProblem::~SHProblem() {
   if (bout_) hipFree(bout_);
   if (bout_h_) hipHostFree(bout_h_);
   if (rtab_) hipFree(rtab_);
+  if (rtab_mixed_) hipFree(rtab_mixed_);
   if (ev_in_) hipEventDestroy(ev_in_);
   if (ev_out_) hipEventDestroy(ev_out_);
   if (side_) hipStreamDestroy(side_);
@@ -613,17 +614,23 @@ int SHProblem::run_batch(const double* U, double* Unew, int64_t batch, int64_t n
                          double* fnorm, int32_t* status, int64_t* applies, double* shift) {
   if (status_) return status_;
   // refusals come before anything is launched or allocated
-  const bool pc = kind == NK_PC_SPECTRAL;
+  const bool mixed = kind == NK_PC_SPECTRAL_MIXED, pc = kind == NK_PC_SPECTRAL || mixed;
   if ((kind != NK_PC_NONE && !pc) || !U || !Unew || batch < 1 || batch > 0x7fffffff ||
       nsteps < 1 || inner_maxiter < 1 || dist() || ny_g_ != ny_ || !(c_.k > 0.0) ||
       !std::isnan(o.f_rtol) || !std::isnan(o.x_tol) || !std::isnan(o.x_rtol))
     return NK_EINVAL;
-  if (pc ? !shlin_resident_pc_fits(ny_, nx_) || fftpc_check(ny_, nx_, h_, r_, c_.k)
-         : !shlin_resident_fits(ny_, nx_))
+  if (mixed ? !shlin_resident_pcm_fits(ny_, nx_) || fftpc_check_mixed(ny_, nx_, h_, r_, c_.k)
+      : pc  ? !shlin_resident_pc_fits(ny_, nx_) || fftpc_check(ny_, nx_, h_, r_, c_.k)
+            : !shlin_resident_fits(ny_, nx_))
     return NK_EINVAL;
-  if (pc && !rtab_) {
-    std::vector<double> tab(size_t(nx_ + ny_));
-    shlin_resident_pc_tables(ny_, nx_, tab.data());
+  double*& rtab = mixed ? rtab_mixed_ : rtab_;
+  if (pc && !rtab) {
+    std::vector<double> tab(mixed ? shlin_resident_pcm_table_doubles(ny_, nx_)
+                                  : size_t(nx_ + ny_));
+    if (mixed)
+      shlin_resident_pcm_tables(ny_, nx_, tab.data());
+    else
+      shlin_resident_pc_tables(ny_, nx_, tab.data());
     double* d = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * tab.size()) != hipSuccess) {
       (void)hipGetLastError();
@@ -634,7 +641,7 @@ int SHProblem::run_batch(const double* U, double* Unew, int64_t batch, int64_t n
       (void)hipFree(d);
       return NK_EHIP;
     }
-    rtab_ = d;
+    rtab = d;
   }
   if (batch > bout_cap_) {  // the last call synchronised: nothing reads the old entries
     ShResidentOut *d = nullptr, *h = nullptr;
@@ -671,10 +678,11 @@ int SHProblem::run_batch(const double* U, double* Unew, int64_t batch, int64_t n
   A.inner_maxiter = inner_maxiter;
   A.nsteps = nsteps;
   A.line_search = o.line_search ? 1 : 0;
-  A.tables = pc ? rtab_ : nullptr;
+  A.tables = pc ? rtab : nullptr;
   A.ih2 = e;
   A.out = bout_;
-  hipError_t e1 = sh_resident_launch(A, batch, E_.s);
+  hipError_t e1 =
+      mixed ? sh_resident_pcm_launch(A, batch, E_.s) : sh_resident_launch(A, batch, E_.s);
   if (e1 == hipSuccess)
     e1 = hipMemcpyAsync(bout_h_, bout_, sizeof(*bout_) * batch, hipMemcpyDeviceToHost, E_.s);
   if (e1 != hipSuccess) return NK_EHIP;

@@ -53,7 +53,8 @@ class SHProblem final : public Problem {
   // launch of sh_resident.hip: one workgroup per state runs Newton-CG on chip with the analytic
   // Jacobian, whatever jvp_mode and set_precond say.  kind: NK_PC_NONE (plain CG; sides >= 5,
   // ny nx <= kShLinResidentMaxPoints) or NK_PC_SPECTRAL (ny, nx powers of two in [8, 128],
-  // ny nx <= kShLinResidentPcMaxPoints, k r < 2).  o gives f_tol, Newton's maxiter and line_search;
+  // ny nx <= kShLinResidentPcMaxPoints, k r < 2) or NK_PC_SPECTRAL_MIXED (sh_resident_pcm.hip: the
+  // grids of shlin_resident_pcm_fits, k r < 2).  o gives f_tol, Newton's maxiter and line_search;
   // the other tolerances must be unset.  r, g: per-member device arrays, or null for the
   // problem's values.  A member refused (k (g^2/6 + r/2) >= 1; spectral: k r >= 2) or stopped
   // (NK_NONFINITE, NK_NO_CONVERGENCE) leaves its last accepted state in Unew; the others go on.
@@ -111,11 +112,13 @@ class SHProblem final : public Problem {
   FftPcPlan pc_{};            // spectral preconditioner (tables != nullptr once built)
   bool pc_on_ = false;
   // run_batch's per-member results (device entries and their pinned host copy, grown on demand)
-  // and the resident kernel's twiddle table
+  // and the resident kernels' tables (NK_PC_SPECTRAL's twiddles; NK_PC_SPECTRAL_MIXED's roots and
+  // permutations)
   ShResidentOut* bout_ = nullptr;
   ShResidentOut* bout_h_ = nullptr;
   int64_t bout_cap_ = 0;
   double* rtab_ = nullptr;
+  double* rtab_mixed_ = nullptr;
 };
 
 // newton_krylov(F, xin) for an arbitrary device residual (droplet.py:383, PMA2_nk.py:100, ...):

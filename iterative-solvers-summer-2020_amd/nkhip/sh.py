@@ -15,7 +15,9 @@ the finite-difference JVP and the Arnoldi BLAS-1 work are HIP kernels, the host 
 
 ``run_batch`` / ``step_batch`` serve small grids (ny*N <= ``resident_max_points``) and ensembles of
 them: one workgroup per state runs whole implicit steps on chip, Newton-CG with the analytic
-Jacobian, in one launch for the batch (csrc/sh_resident.hip).
+Jacobian, in one launch for the batch (csrc/sh_resident.hip).  ``precond="spectral"`` preconditions
+CG inside the workgroup on power-of-two sides, ``precond="spectral-mixed"`` on even sides
+2^a 3^b 5^c in [6, 128] that are not both powers of two (csrc/sh_resident_pcm.hip).
 """
 from __future__ import annotations
 
@@ -168,6 +170,9 @@ class SwiftHohenberg:
     #: the cap of ``run_batch(..., precond="spectral")`` in grid points (host only; 128 x 64)
     resident_precond_max_points = int(lib.nk_shlin_resident_precond_max_points())
 
+    #: the cap of ``run_batch(..., precond="spectral-mixed")`` in grid points (host only; 96 x 96)
+    resident_precond_mixed_max_points = int(lib.nk_shlin_resident_precond_mixed_max_points())
+
     def run_batch(self, U, nsteps=1, r=None, g=None, precond=None, inner_maxiter=1000):
         """``nsteps`` implicit steps of B independent states in one launch, one workgroup per state
         with whole steps on chip (csrc/sh_resident.hip): for small grids, where ``step`` is bound
@@ -192,18 +197,23 @@ class SwiftHohenberg:
         M = ((1 + sigma) I - L k/2)^-1, sigma = max(mean k (1.5 u^2 - g u), 0), applied inside the
         workgroup: the iteration count no longer grows as the mesh is refined.  It needs N and ny
         powers of two in [8, 128], ny*N <= ``resident_precond_max_points`` and k r < 2.
-        ``set_precond`` / ``inner_M`` and ``jvp`` have no effect here.  Anything else
-        (``"spectral-mixed"``, another grid, a stepper with ``f_rtol``, ``x_tol`` or ``x_rtol``
-        set, with a communicator or a slab of a larger grid) raises ``ValueError`` and leaves the
-        stepper usable.
+        ``"spectral-mixed"`` is the same solve (M, sigma, forcing, line search, guards, counters)
+        with wave-local mixed-radix transforms (csrc/sh_resident_pcm.hip), for N and ny even, of
+        the form 2^a 3^b 5^c, in [6, 128] and not both powers of two, ny*N <=
+        ``resident_precond_mixed_max_points`` and k r < 2 (96 x 96, 128 x 72 and 72 x 128 fit; a
+        grid whose plane, spectrum and tables exceed a workgroup's LDS raises).  A grid whose sides
+        are both powers of two raises under this name: ``"spectral"`` serves it.
+        ``set_precond`` / ``inner_M`` and ``jvp`` have no effect here.  Anything else (another
+        grid, a stepper with ``f_rtol``, ``x_tol`` or ``x_rtol`` set, with a communicator or a slab
+        of a larger grid) raises ``ValueError`` and leaves the stepper usable.
 
         A member's bits depend on its own inputs alone.  A member with k (g^2/6 + r/2) >= 1 (or,
-        under ``"spectral"``, k r >= 2) is refused as a non-finite one is; a member that fails a
+        under either preconditioner, k r >= 2) is refused as a non-finite one is; a member that fails a
         step stops with the last state it completed a step to.  ``NoConvergence`` (carrying
         ``U_new``) or the non-finite error is raised after ``last_batch`` and ``last_batch_state``
         are filled, the other members' results among them."""
-        if precond not in (None, "none", "spectral"):
-            raise ValueError(f"precond={precond!r}: None, 'none' or 'spectral'")
+        if precond not in (None, "none", "spectral", "spectral-mixed"):
+            raise ValueError(f"precond={precond!r}: None, 'none', 'spectral' or 'spectral-mixed'")
         if self.comm is not None or self.ny_local != self.ny:
             raise ValueError("run_batch serves one GPU: no communicator, ny_local == ny")
         o = self.opts
@@ -217,6 +227,24 @@ class SwiftHohenberg:
                                  f"<= {self.resident_precond_max_points}, got {ny} x {nx}")
             if not self.k * self.r < 2:
                 raise ValueError("precond='spectral' needs k r < 2")
+        elif precond == "spectral-mixed":
+            def side(v):
+                if v < 6 or v > 128 or v % 2:
+                    return False
+                for f in (2, 3, 5):
+                    while v % f == 0:
+                        v //= f
+                return v == 1
+            pow2 = lambda v: v & (v - 1) == 0  # noqa: E731
+            if not (side(ny) and side(nx) and n <= self.resident_precond_mixed_max_points):
+                raise ValueError(f"precond='spectral-mixed': N and ny even, 2^a 3^b 5^c, in "
+                                 f"[6, 128] with ny*N <= {self.resident_precond_mixed_max_points}, "
+                                 f"got {ny} x {nx}")
+            if pow2(ny) and pow2(nx):
+                raise ValueError(f"precond='spectral-mixed': {ny} x {nx} has two power-of-two "
+                                 f"sides; precond='spectral' serves it")
+            if not self.k * self.r < 2:
+                raise ValueError("precond='spectral-mixed' needs k r < 2")
         elif min(ny, nx) < 5 or n > self.resident_max_points:
             raise ValueError(f"run_batch: sides >= 5 and ny*N <= {self.resident_max_points}, "
                              f"got {ny} x {nx}")
@@ -248,11 +276,15 @@ class SwiftHohenberg:
         mine = self._stream if self._stream is not None else cur
         if mine != cur:
             mine.wait_stream(cur)
-        kind = _lib.NK_PC_SPECTRAL if precond == "spectral" else _lib.NK_PC_NONE
+        kind = {"spectral": _lib.NK_PC_SPECTRAL,
+                "spectral-mixed": _lib.NK_PC_SPECTRAL_MIXED}.get(precond, _lib.NK_PC_NONE)
         rc = lib.nk_sh_run_batch(self._h, ptr(U), ptr(new), B, int(nsteps), ptr(r), ptr(g), kind,
                                  int(inner_maxiter), ptr(res["nit"]), ptr(res["iters"]),
                                  ptr(res["steps"]), ptr(res["fnorm"]), ptr(res["status"]),
                                  ptr(res["precond"]), ptr(res["shift"]))
+        if rc == _lib.NK_EINVAL and precond == "spectral-mixed":  # the one refusal left to the host
+            raise ValueError(f"precond='spectral-mixed': the plane, spectrum and tables of "
+                             f"{ny} x {nx} exceed a workgroup's LDS")
         check(min(rc, 0), "nk_sh_run_batch")
         self.last_batch, self.last_batch_state = res, new
         raise_for_status(rc, new)
